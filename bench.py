@@ -40,8 +40,19 @@ frame x frames per launch); the latency-bound tracking stages are
 reported per frame in stage_ms_per_frame.  cpu_baseline — the oracle (CPU restatement: OpenMP
 SuperPoint + the same tracking loop over the CPU stages) on a bounded prefix of the same sequence.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full] [--dump-outputs DIR]
        (N > 1 is launched by torch.distributed.run; see the driver contract.)
+The drive's length does not follow --steps: W + K above the default command's 25 steps track the same 25
+steps again from the drive's first frame, each lap with a fresh tracker, map and cloud (lap_schedule; the
+restart is inside the timed region), so a step's work and the frames to render stay those of the drive the
+tests pin.
+A plain run renders the frames it tracks, warms up, times the K steps and prints the headline (value,
+ms_per_step, the trajectory's ATE and the roofline of the timed region's own events).  --full adds every
+other figure described above — the stage-profiled steps, input_upload, the network alone, frontend_batch,
+monocular_hd, local_ba and cpu_baseline; the other options select among those and mean nothing without it.
+--dump-outputs DIR writes what the tracker returned for the last timed step and holds after it
+(dump_outputs) as DIR/<name>.npy; the input is seeded, so two runs with the same arguments compare
+array for array.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -198,6 +209,25 @@ def headline_plan(B, warmup, steps, profile_steps):
     return n_path, ranges
 
 
+LAP_WARMUP, LAP_STEPS = 5, 20   # the default command's schedule: one lap of the drive is their 25 steps
+
+
+def lap_schedule(warmup, steps, lap_steps):
+    """The warm-up and timed steps as segments (restart, k0, k1, timed) of the drive's steps k0..k1-1:
+    step g of the run is step g % lap_steps of the drive, a segment ends where the warm-up, the run or
+    the lap ends, and restart marks the segments that begin a lap (the run's first needs no restart:
+    the tracker is new).  Up to lap_steps steps in all: the schedule headline_plan gives."""
+    segs = []
+    for a, b, timed in ((0, warmup, False), (warmup, warmup + steps, True)):
+        g = a
+        while g < b:
+            k0 = g % lap_steps
+            k1 = min(k0 + (b - g), lap_steps)
+            segs.append((k0 == 0, k0, k1, timed))
+            g += k1 - k0
+    return segs
+
+
 def run_tracker_steps(slam, bgr, dep, hdep, B, k0, k1):
     """Steps k0..k1-1 of the headline through vs_slam_process_batch_dev: step k = processed frames
     kB..kB+B-1 (device frames bgr[kB], depth dep[kB]; host depth hdep; TUM-like timestamps, FRAME_STEP
@@ -269,6 +299,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5, help="untimed steps (5: the driver's own command)")
     ap.add_argument("--batch", type=int, default=32, help="frames per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: stage-profiled steps, input_upload, the "
+                         "network alone, frontend_batch, monocular_hd, local_ba, cpu_baseline (the options below "
+                         "select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the tracker's outputs after the last timed step as DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-frames", type=int, default=24, help="cpu_baseline sample size (processed frames)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--frontend-steps", type=int, default=4, help="timed steps of the config[3] batch front end")
@@ -284,7 +320,33 @@ def parse():
     ap.add_argument("--render-workers", type=int, default=0,
                     help="processes rendering the synthetic sequence (0: min(16, cpus / ranks); 1 under rocprofv3 "
                          "--pmc, whose preloaded library has initialised the GPU before the fork)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.batch < 1:
+        ap.error("--steps and --batch must be >= 1, --warmup >= 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, slam, last_step):
+    """--dump-outputs: what a caller of vs_slam_process_batch_dev holds after the last timed step — the
+    step's per-frame results (tracked, f32 0/1) and, read back through the C ABI before anything else
+    runs, the unsmoothed trajectory of every frame tracked so far (ids, timestamps, R, t: f64) and the
+    map (positions f64, validity flags f32).  One .npy per array; the set stays far below
+    DUMP_LIMIT_BYTES at any drive bench.py accepts (the map is a few ten thousand points)."""
+    ids, ts, R, t = slam.trajectory()
+    pos, valid = slam.map_points()
+    arrays = {"tracked": np.asarray(last_step, np.float32),
+              "trajectory_ids": ids.astype(np.float64), "trajectory_timestamps": ts.astype(np.float64),
+              "trajectory_R": R.astype(np.float64), "trajectory_t": t.astype(np.float64),
+              "map_points": pos.astype(np.float64), "map_valid": valid.astype(np.float32)}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def cpu_baseline(L, nframes, ba=None):
@@ -689,13 +751,27 @@ def main():
     # and the ranks all-gather them (replicas: every GPU tracks the same drive).  The closed loop
     # (synth.loop_sequence) is the monocular stream's (config[4]); config[3] renders its own drive frames.
     workers = args.render_workers or max(1, min(16, (os.cpu_count() or 1) // max(world, 1)))
-    n_path, ranges = headline_plan(B, args.warmup, args.steps,
-                                   args.track_profile_steps if args.stage_profile != "all" else 0)
+    # The drive is always the one of the default command (LAP_WARMUP + LAP_STEPS steps and the profiled
+    # steps: 928 frames at B = 32), the length the tracker is pinned on; a longer schedule tracks it
+    # again from its first frame with a fresh tracker (lap_schedule), so the frames to render and the
+    # map a step works on do not grow with --steps.
+    profile_steps = args.track_profile_steps if args.stage_profile != "all" else 0
+    n_path, _ = headline_plan(B, LAP_WARMUP, LAP_STEPS, profile_steps)
+    lap_steps = LAP_WARMUP + LAP_STEPS
+    segments = lap_schedule(args.warmup, args.steps, lap_steps)
+    ranges = [(0, args.warmup), (args.warmup, args.warmup + args.steps)]
+    end = segments[-1][2]  # the last tracker's position on the drive after the timed steps
+    if args.full and profile_steps > 0:  # on the same tracker where the drive has the frames left
+        p0 = end if (end + profile_steps) * B <= n_path else 0
+        ranges.append((p0, p0 + profile_steps))
     poses = synth.pioneer_trajectory(n_path)
-    mine = list(range(rank, n_path, world))
+    # a plain run renders the frames its steps track (the poses are those of the whole drive: the
+    # timed frames are the same images with and without --full)
+    n_render = n_path if args.full else max(k1 for _, _, k1, _ in segments) * B
+    mine = list(range(rank, n_render, world))
     pb, pd = synth.render_frames(poses, mine, workers=workers)
     if world > 1:
-        per = (n_path + world - 1) // world
+        per = (n_render + world - 1) // world
         gb = torch.zeros((world, per) + pb.shape[1:], dtype=torch.uint8, device=dev)
         gd = torch.zeros((world, per) + pd.shape[1:], dtype=torch.float32, device=dev)
         lb = torch.zeros((per,) + pb.shape[1:], dtype=torch.uint8, device=dev)
@@ -704,7 +780,7 @@ def main():
         ld[:len(mine)].copy_(torch.from_numpy(pd))
         dist.all_gather_into_tensor(gb, lb)
         dist.all_gather_into_tensor(gd, ld)
-        order = [(i % world, i // world) for i in range(n_path)]
+        order = [(i % world, i // world) for i in range(n_render)]
         bgr = torch.stack([gb[r, j] for r, j in order])
         dep = torch.stack([gd[r, j] for r, j in order])
         del gb, gd, lb, ld
@@ -714,24 +790,44 @@ def main():
     del pb, pd
     Lp = dict(t_wc=np.stack([p[1] for p in poses]), R_wc=np.stack([p[0] for p in poses]))
     hdep_all = dep.cpu().numpy()  # the tracker keeps host copies of live frames' depth
-    hdep = [hdep_all[i] for i in range(n_path)]
+    hdep = [hdep_all[i] for i in range(n_render)]
     Lp["depth"] = hdep_all
-    progress(f"{n_path}-frame drive rendered ({len(mine)} frames on this rank)")
+    progress(f"{n_render} frames of the {n_path}-frame drive rendered ({len(mine)} on this rank)")
 
     ctx = vslam_abi.Context(local if world > 1 else 0)
-    slam = vslam_abi.Slam(ctx, max_batch=B)
-    dense = vslam_abi.Dense(ctx)  # main.cpp:1116-1139: every processed frame fused into the dense cloud
-    slam.attach_dense(dense)
+    slam = dense = None
+
+    def fresh_tracker():
+        nonlocal slam, dense
+        if slam is not None:
+            slam.close()
+            dense.close()
+        slam = vslam_abi.Slam(ctx, max_batch=B)
+        dense = vslam_abi.Dense(ctx)  # main.cpp:1116-1139: every processed frame fused into the dense cloud
+        slam.attach_dense(dense)
+
+    fresh_tracker()
 
     progress(f"sequence rendered, tracker ready; {args.warmup} warmup steps")
 
     def run_steps(k0, k1):
         # never prefetched across the warmup / timed boundary: every timed batch is extracted inside
         # the timed region
-        run_tracker_steps(slam, bgr, dep, hdep, B, k0, k1)
+        return run_tracker_steps(slam, bgr, dep, hdep, B, k0, k1)
+
+    def run_segments(timed):
+        # a segment that starts a lap again (after the run's first) drops the tracker, its map and its
+        # cloud for fresh ones: inside the timed region that is part of the step's time
+        out = []
+        for i, (restart, k0, k1, seg_timed) in enumerate(segments):
+            if seg_timed == timed:
+                if restart and i > 0:
+                    fresh_tracker()
+                out += run_steps(k0, k1)
+        return out
 
     torch.cuda.synchronize()
-    run_steps(*ranges[0])
+    run_segments(False)
     torch.cuda.synchronize()
     ctx.tie_stats(reset=True)
     # headline: per-stage events on the extraction stages only (the roofline kernel); the tracking
@@ -743,7 +839,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run_steps(*ranges[1])
+    timed_results = run_segments(True)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -758,11 +854,17 @@ def main():
         elapsed = float(tt.item())
     frames_timed = B * args.steps
     value = world * frames_timed / elapsed
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, slam, timed_results[-B:])
+        progress(f"outputs written to {args.dump_outputs}")
 
     # per-stage times of the tracking stages: a few more steps with every stage's events on (kept
     # out of the timed region; the tracker and the ATE below include these frames)
     prof_trk, frames_trk = prof, frames_timed
     if len(ranges) > 2:
+        if ranges[2][0] != end:
+            fresh_tracker()
         ctx.profile(True)
         ctx.profile_reset()
         run_steps(*ranges[2])
@@ -775,7 +877,7 @@ def main():
     # Frame.cpp:25-29): one batch of BGR + depth from pinned host memory into HBM, timed alone — the
     # headline keeps the frames resident (the boundary takes device pointers)
     upload = None
-    if B > 0:
+    if args.full:
         hb = torch.empty(tuple(bgr[:B].shape), dtype=torch.uint8, pin_memory=True)
         hd = torch.empty(tuple(dep[:B].shape), dtype=torch.float32, pin_memory=True)
         hb.copy_(bgr[:B].cpu())
@@ -840,7 +942,7 @@ def main():
     # the dominant kernel alone: one extraction chunk (8 frames) and a whole step (B frames) through
     # the network on the whole chip, nothing else running (HIP events on the launch stream)
     alone = {}
-    for nb in (8, B):
+    for nb in ((8, B) if args.full else ()):
         semi_t = torch.zeros((nb, 60, 80, vslam_abi.SEMI_CH), dtype=torch.float32, device=dev)
         dg_t = torch.zeros((nb, 60, 80, vslam_abi.DESC_DIM), dtype=torch.float32, device=dev)
         sa = torch.cuda.current_stream().cuda_stream
@@ -876,8 +978,8 @@ def main():
                                            "the next frame's speculative chain (frame vs reference keyframe), one pair "
                                            f"per launch on the chain's {spec_cus} CUs, off the critical path")}
     fe = None
-    progress("config[3] batch front end")
-    if not args.no_frontend and args.frontend_steps > 0:
+    if args.full and not args.no_frontend and args.frontend_steps > 0:
+        progress("config[3] batch front end")
         fe = frontend_batch(ctx, args.frontend_frames, rank, world, args.frontend_steps, 1, workers)
         P = fe.pop("_match_pairs")
         mroof["frontend_batch"] = match_roofline(fe.pop("_match"), P, 256,
@@ -889,18 +991,18 @@ def main():
             mroof["frontend_batch"]["in_pipeline_avg_launch_us"] = round(inp[0] * 1e3 / inp[1], 2)
 
     mono = None
-    progress("config[4] monocular HD stream")
-    if args.mono_steps > 0:
+    if args.full and args.mono_steps > 0:
+        progress("config[4] monocular HD stream")
         mono = monocular_hd(ctx, B, rank, world, args.mono_steps, 1, workers)
 
     lba, lba_problem = None, None
-    if args.ba_reps > 0:
+    if args.full and args.ba_reps > 0:
         progress("config[2] local BA stress window")
         lba, lba_problem = local_ba(ctx, args.ba_reps)
 
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             progress("cpu baseline")
             cpu = cpu_baseline(dict(bgr=bgr[:args.cpu_frames].cpu().numpy(), depth=hdep_all[:args.cpu_frames]),
                                args.cpu_frames, lba_problem)
@@ -913,6 +1015,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": "weak",
@@ -926,10 +1029,16 @@ def main():
                             "+ PnP + keyframes + loop closure every 200 keyframes, RTS at the end) and the main "
                             "loop's dense voxel fusion of every processed frame (main.cpp:1116-1139), on a "
                             f"non-repeating {n_path}-frame Pioneer-like drive (synth.pioneer_trajectory: the "
-                            "reference sequence's 848 processed frames or more; every tracked frame distinct)",
+                            "reference sequence's 848 processed frames or more; every frame of a lap distinct; "
+                            f"more than {lap_steps} warm-up and timed steps track it again from its first frame "
+                            "with a fresh tracker, inside the timed region)",
                 "path_frames": n_path,
-                "timed_frames_distinct": frames_timed,
-                "timed_frames": [ranges[1][0] * B, ranges[1][1] * B - 1],
+                "rendered_frames": n_render,
+                "lap_steps": lap_steps,
+                "tracker_restarts": sum(1 for i, sg in enumerate(segments) if sg[0] and i > 0),
+                "timed_frames_distinct": B * len({k for _, k0, k1, t in segments if t for k in range(k0, k1)}),
+                "timed_segments": [[k0 * B, k1 * B - 1] for _, k0, k1, t in segments if t][:8],
+                "timed_frames": [ranges[1][0] * B, ranges[1][1] * B - 1] if ranges[1][1] <= lap_steps else None,
                 "parity": "tests/test_gpu_headline_drive.py: this drive and schedule (headline_plan, "
                           "run_tracker_steps) == the oracle tracker bit for bit, and its op log replayed "
                           "through the independent glue restatement (tests/slam_glue_ref.py)",
@@ -1014,6 +1123,7 @@ def main():
             "monocular_hd": mono,
             "local_ba": lba,
             "cpu_baseline": cpu,
+            "dumped_outputs": dumped,
         }
         print(json.dumps(result), flush=True)
     slam.close()

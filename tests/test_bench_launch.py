@@ -162,3 +162,63 @@ def test_share_batch_id_reaches_every_rank(world):
         p.join(60)
     assert all(got[r] == bytes(range(7, 135)) for r in range(world))
     assert bench.share_batch_id(0, 1, lambda: b"x") is None
+
+
+# ---- the plain run's options: --full and --dump-outputs ----
+def test_full_and_dump_outputs_are_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 3, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_timed_steps_follow_the_steps_option():
+    """lap_schedule: --steps sets the number of timed steps at any length; the default command is
+    headline_plan's schedule on one tracker, a longer one tracks the same 25 steps of the drive again
+    (restart) and never a step beyond them."""
+    lap = bench.LAP_WARMUP + bench.LAP_STEPS
+    n_path, ranges = bench.headline_plan(32, bench.LAP_WARMUP, bench.LAP_STEPS, 4)
+    assert lap == 25 and n_path == 928
+    assert bench.lap_schedule(5, 20, lap) == [(True, 0, 5, False), (False, 5, 25, True)]
+    assert [(k0, k1) for _, k0, k1, _ in bench.lap_schedule(5, 20, lap)] == ranges[:2]
+    assert bench.lap_schedule(0, 3, lap) == [(True, 0, 3, True)]
+    assert bench.lap_schedule(1, 3, lap) == [(True, 0, 1, False), (False, 1, 4, True)]
+    assert bench.lap_schedule(5, 288, lap)[:3] == [(True, 0, 5, False), (False, 5, 25, True), (True, 0, 25, True)]
+    assert bench.lap_schedule(30, 2, lap) == [(True, 0, 25, False), (True, 0, 5, False), (False, 5, 7, True)]
+    for warmup, steps in ((0, 1), (3, 2), (5, 20), (5, 21), (5, 288), (26, 1000), (25, 25)):
+        segs = bench.lap_schedule(warmup, steps, lap)
+        assert sum(k1 - k0 for _, k0, k1, timed in segs if timed) == steps
+        assert sum(k1 - k0 for _, k0, k1, timed in segs if not timed) == warmup
+        assert all(0 <= k0 < k1 <= lap and restart == (k0 == 0) for restart, k0, k1, _ in segs)
+        pos = 0  # consecutive segments continue the lap or restart it at its end
+        for restart, k0, k1, _ in segs:
+            assert k0 == pos % lap
+            pos = k1
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """dump_outputs: one float32 / float64 .npy per array the tracker hands back, under the size limit."""
+    import numpy as np
+
+    class Tracker:
+        def trajectory(self):
+            n = 5
+            return (np.arange(n, dtype=np.int32) * 3, 1e9 + 0.1 * np.arange(n), np.tile(np.eye(3), (n, 1, 1)),
+                    np.arange(3.0 * n).reshape(n, 3))
+
+        def map_points(self):
+            return np.arange(21.0).reshape(7, 3), np.array([1, 0, 1, 1, 0, 1, 1], np.uint8)
+
+    shapes = bench.dump_outputs(str(tmp_path / "out"), Tracker(), [True, False, True, True])
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == sorted(k + ".npy" for k in shapes) and "tracked.npy" in files
+    arrays = {f[:-4]: np.load(tmp_path / "out" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= bench.DUMP_LIMIT_BYTES == 64 << 20
+    assert arrays["tracked"].tolist() == [1.0, 0.0, 1.0, 1.0]
+    assert arrays["trajectory_ids"].tolist() == [0.0, 3.0, 6.0, 9.0, 12.0]
+    assert np.array_equal(arrays["trajectory_t"], Tracker().trajectory()[3])
+    assert arrays["map_valid"].tolist() == [1.0, 0.0, 1.0, 1.0, 0.0, 1.0, 1.0]
+    assert {k: list(a.shape) for k, a in arrays.items()} == shapes

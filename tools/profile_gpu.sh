@@ -6,10 +6,10 @@
 export TMPDIR=/tmp
 R=$(pwd)
 OUT=$R/gpurun_out
-# Single-size passes: --no-frontend --mono-steps 0 leaves only the tracker, whose network launches are
+# Single-size passes: --full --no-frontend --mono-steps 0 leaves only the tracker (with its profiled steps), whose network launches are
 # all one extraction chunk (8 frames), so per-launch durations and bytes divide by one frame count.
-ARGS=${BENCH_ARGS:---steps 5 --warmup 1 --no-cpu-baseline --no-frontend --mono-steps 0 --render-workers 1}
-PMC_ARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-frontend --mono-steps 0 --render-workers 1"
+ARGS=${BENCH_ARGS:---full --steps 5 --warmup 1 --no-cpu-baseline --no-frontend --mono-steps 0 --render-workers 1}
+PMC_ARGS="--full --steps 2 --warmup 1 --no-cpu-baseline --no-frontend --mono-steps 0 --render-workers 1"
 mkdir -p $OUT
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_trace -o trace --output-format csv -- \
     python3 $R/bench.py $ARGS > $OUT/prof_trace.log 2>&1 && echo "trace ok" &&

@@ -104,7 +104,7 @@ def main():
                       "grid_sizes": sorted(grids.get(k, ()))}
     doc = {"tag": tag, "frames_per_launch": batch,
            "note": "FETCH_SIZE x2 (gfx950 16-B/lane streaming-read correction), WRITE_SIZE as is; bytes per launch. "
-                   "Taken from bench.py --no-frontend --mono-steps 0: every SuperPoint launch is one tracker "
+                   "Taken from bench.py --full --no-frontend --mono-steps 0: every SuperPoint launch is one tracker "
                    "extraction chunk of frames_per_launch frames (one grid size per network kernel)",
            "kernels": kernels}
     with open(os.path.join(PROF, f"{tag}_pmc_traffic.json"), "w") as fh:
