@@ -494,6 +494,45 @@ int vs_dense_write_ply(vs_dense* d, const char* path);
  * reference's main loop does (NULL detaches). */
 int vs_slam_attach_dense(vs_slam* slam, vs_dense* d);
 
+/* ---- the sparse-map cloud filter (main.cpp:1185-1215 per processed frame, :1340-1368 at the end) ----
+ * A bounding-box clip, statistical_outlier_removal (main.cpp:512-563: a point stays when the mean
+ * distance to its sor_k nearest neighbours is <= mean + sor_std_ratio * std over the cloud) and
+ * surface_aware_filter (:568-642: a point stays when the scatter matrix of its surf_k nearest
+ * neighbours has l1 >= 1e-12 and 1 - l3 / l1 >= surf_min_anisotropy), the second on the first's
+ * survivors.  Both searches are exact in fp64: the distance lists are nanoflann's
+ * ((dx dx + dy dy) + dz dz, self excluded); neighbours are ordered by (d2, index), so among equal
+ * distances the lowest index comes first.  A stage whose input has n <= k points returns it
+ * unchanged, as the reference does.  Coordinates must be finite.  One call per context at a time
+ * (the scratch lives in the context, sized on first use). */
+#define VS_CLOUD_MAX_K 32
+#define VS_CLOUD_MAX_POINTS (1 << 18)
+typedef struct vs_cloud_filter_config {
+    int sor_k; double sor_std_ratio;        /* 25, 0.6; sor_k == 0 skips the stage  */
+    int surf_k; double surf_min_anisotropy; /* 25, 0.4; surf_k == 0 skips the stage */
+    int use_bbox; double bbox_min[3], bbox_max[3]; /* inclusive, main.cpp:1203-1205 */
+} vs_cloud_filter_config;
+void vs_cloud_filter_default_config(vs_cloud_filter_config* cfg);
+/* Stage isolation: the k nearest neighbours of each of the n device points d_pts [n][3] among the
+ * others, d_nbr / d_d2 [n][k] ascending (-1 / +inf past the n - 1 others).  split: workgroups that
+ * share a query block's candidates, 0 = automatic, else forced (<= 64).  Enqueue only. */
+int vs_cloud_knn_dev(vs_ctx* ctx, const double* d_pts, int n, int k, int split, int* d_nbr, double* d_d2,
+                     void* stream);
+/* The filter on device points.  d_out [n][3] and d_idx [n] (indices into the input, ascending)
+ * receive the survivors in input order; d_counts [3] = points {after the box, after
+ * statistical_outlier_removal, after surface_aware_filter}, the last being the number written.
+ * cfg NULL = the reference's values, no box.  Enqueue only.  n > VS_CLOUD_MAX_POINTS or a
+ * k > VS_CLOUD_MAX_K: VS_ERR_CAPACITY. */
+int vs_cloud_filter_dev(vs_ctx* ctx, const double* d_pts, int n, const vs_cloud_filter_config* cfg, double* d_out,
+                        int* d_idx, int* d_counts, void* stream);
+/* The same on host buffers (out [n][3], idx [n]); synchronous. */
+int vs_cloud_filter(vs_ctx* ctx, const double* pts, int n, const vs_cloud_filter_config* cfg, double* out, int* idx,
+                    int counts[3]);
+/* main.cpp:1340-1368 without densify_surfaces, on the tracker's map points in HBM: every map point
+ * (valid_only != 0: the valid ones) inside the trajectory's bounding box +- 3.0 m (no clip without
+ * frames), then both stages with the reference's values.  *n = survivors; the first cap of them go
+ * to pts (x 3) and idx (indices into vs_slam_map's list), each nullable.  Synchronous. */
+int vs_slam_filtered_map(vs_slam* slam, int valid_only, int cap, double* pts, int* idx, int* n);
+
 /* ---- F4: Optimizer::pose_graph_optimize (Optimizer.cpp:654-863), g2o LM restated -------------
  * N keyframe poses (camera -> world, R [N][9] row-major, t [N][3], keyframe order; the first is
  * fixed), odometry edges between consecutive keyframes from these poses, L loop constraints

@@ -1,0 +1,100 @@
+"""Times the sparse-map cloud filter (vs_cloud_filter_dev) and its k-NN stage alone (vs_cloud_knn_dev)
+at the tracking tests' map sizes, with device events over repeated calls after warm-up.
+
+    python tools/bench_cloud.py [--out profiles/cloud_filter.json] [--sizes 12000 60000] [--k 25]
+
+Pair tests per filter call = n0^2 + n1^2 (n0 points enter statistical_outlier_removal, n1 enter
+surface_aware_filter: every query meets every candidate).  One pair test is 3 sub, 3 mul, 2 add and
+1 compare in fp64, none of them fused; the fp64 VALU peak used for the share is 78.6 TFLOP/s counting
+an FMA as two, i.e. 39.3e12 unfused instructions per second per lane-op."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "visual-slam-pipeline_amd", "python"))
+import vslam_abi  # noqa: E402
+
+PEAK_FP64_OPS = 39.3e12  # unfused fp64 VALU instructions (lane-ops) per second, MI355X
+OPS_PER_PAIR = 9
+
+
+def cloud(n, seed=1):
+    """Two noisy planes, a volumetric blob and 2 % far outliers (the shape of a sparse indoor map)."""
+    rng = np.random.default_rng(seed)
+    n_out, n_pl = n // 50, (n - n // 50) * 3 // 8
+    uv = rng.uniform(0, 4, (2, n_pl, 2))
+    a = np.column_stack([uv[0], 0.002 * rng.standard_normal(n_pl)])
+    b = np.column_stack([0.002 * rng.standard_normal(n_pl) + 4.5, uv[1]])
+    blob = rng.uniform(0, 1.5, (n - n_out - 2 * n_pl, 3)) + [1.0, 4.5, 1.0]
+    return rng.permutation(np.concatenate([a, b, blob, rng.uniform(-12, 12, (n_out, 3))]))
+
+
+def timed(fn, stream, warm, reps, rounds=5):
+    """ms per call: events on the stream the calls are enqueued on, around reps calls, per round."""
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(rounds):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(reps):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1) / reps)
+    return ms
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--sizes", type=int, nargs="+", default=[12000, 60000])
+    ap.add_argument("--k", type=int, default=25)
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    res = {"device": torch.cuda.get_device_name(0), "cus": cus, "k": args.k, "runs": []}
+    with vslam_abi.Context(0) as ctx:
+        cfg = ctx.cloud_config(sor_k=args.k, surf_k=args.k)
+        stream = torch.cuda.ExternalStream(ctx.stream)  # the context's own stream
+        s = stream.cuda_stream
+        for n in args.sizes:
+            p = torch.from_numpy(cloud(n)).to(dev)
+            out = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+            idx = torch.zeros(n, dtype=torch.int32, device=dev)
+            cnt = torch.zeros(3, dtype=torch.int32, device=dev)
+            nbr = torch.zeros((n, args.k), dtype=torch.int32, device=dev)
+            d2 = torch.zeros((n, args.k), dtype=torch.float64, device=dev)
+            reps = max(10, int(2e10 / (n * n)))
+            f_ms = timed(lambda: ctx.cloud_filter_dev(p.data_ptr(), n, cfg, out.data_ptr(), idx.data_ptr(),
+                                                      cnt.data_ptr(), s), stream, 5, reps)
+            k_ms = timed(lambda: ctx.cloud_knn_dev(p.data_ptr(), n, args.k, nbr.data_ptr(), d2.data_ptr(), 0, s),
+                         stream, 5, reps)
+            c = cnt.cpu().numpy().tolist()
+            blocks = (n + 255) // 256
+            split = max(1, min(-(-cus // blocks), n // 512, 64))  # cloud.hip knn_split
+            pairs_f, pairs_k = float(c[0]) ** 2 + float(c[1]) ** 2, float(n) ** 2
+            run = {"n": n, "counts": c, "split": split, "reps_per_round": reps,
+                   "filter_ms_rounds": f_ms, "filter_ms": float(np.median(f_ms)),
+                   "knn_ms_rounds": k_ms, "knn_ms": float(np.median(k_ms))}
+            run["filter_pair_tests_per_s"] = pairs_f / (run["filter_ms"] * 1e-3)
+            run["knn_pair_tests_per_s"] = pairs_k / (run["knn_ms"] * 1e-3)
+            run["filter_share_of_fp64_valu_peak"] = run["filter_pair_tests_per_s"] * OPS_PER_PAIR / PEAK_FP64_OPS
+            run["knn_share_of_fp64_valu_peak"] = run["knn_pair_tests_per_s"] * OPS_PER_PAIR / PEAK_FP64_OPS
+            res["runs"].append(run)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -2333,4 +2333,52 @@ int vs_slam_map(vs_slam* sl, int cap, double* pos, uint8_t* valid, int* n) {
     return VS_OK;
 }
 
+// main.cpp:1340-1368 (and :1185-1215 per processed frame) without densify_surfaces, on the map's
+// device mirror: the trajectory's bounding box +- 3.0 m, then the two k-NN filters (cloud.hip)
+int vs_slam_filtered_map(vs_slam* sl, int valid_only, int cap, double* pts, int* idx, int* n) {
+    VS_ARG(sl && n && cap >= 0, "vs_slam_filtered_map: null argument");
+    GpuOps& o = sl->ops;
+    const auto& m = sl->trk->map();
+    const int M = m.size();
+    *n = 0;
+    if (M > VS_CLOUD_MAX_POINTS) {
+        set_error("vs_slam_filtered_map: more than VS_CLOUD_MAX_POINTS map points");
+        return VS_ERR_CAPACITY;
+    }
+    if (M == 0) return VS_OK;
+    VS_ARG(o.map_n == M, "vs_slam_filtered_map: the device map is behind the host map (an earlier call failed)");
+    VS_HIP(hipSetDevice(o.ctx->device));
+    vs_cloud_filter_config c;
+    vs_cloud_filter_default_config(&c);
+    if (!m.frames.empty()) {  // main.cpp:1349-1357
+        c.use_bbox = 1;
+        for (int a = 0; a < 3; a++) {
+            double lo = 1e9, hi = -1e9;
+            for (const auto& f : m.frames) {
+                lo = std::min(lo, f->t[a]);
+                hi = std::max(hi, f->t[a]);
+            }
+            c.bbox_min[a] = lo - 3.0;
+            c.bbox_max[a] = hi + 3.0;
+        }
+    }
+    if (valid_only) VS_CHECK(o.sync_valid(m));
+    const size_t pb = ((size_t)M * 3 * sizeof(double) + 255) & ~(size_t)255, ib = ((size_t)M * sizeof(int) + 255) & ~(size_t)255;
+    VS_CHECK(o.map_tmp.ensure(pb + ib + 3 * sizeof(int)));
+    double* d_out = o.map_tmp.as<double>();
+    int* d_idx = reinterpret_cast<int*>(o.map_tmp.as<char>() + pb);
+    int* d_counts = reinterpret_cast<int*>(o.map_tmp.as<char>() + pb + ib);
+    VS_CHECK(vs::cloud_filter(o.ctx, o.map_pos.as<double>(), M, valid_only ? o.map_valid.as<uint8_t>() : nullptr, c,
+                              d_out, d_idx, d_counts, o.s));
+    int counts[3] = {0, 0, 0};
+    VS_HIP(hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, o.s));
+    VS_HIP(hipStreamSynchronize(o.s));
+    *n = counts[2];
+    const int w = std::min(cap, counts[2]);
+    if (w > 0 && pts) VS_HIP(hipMemcpyAsync(pts, d_out, (size_t)w * 3 * sizeof(double), hipMemcpyDeviceToHost, o.s));
+    if (w > 0 && idx) VS_HIP(hipMemcpyAsync(idx, d_idx, (size_t)w * sizeof(int), hipMemcpyDeviceToHost, o.s));
+    VS_HIP(hipStreamSynchronize(o.s));
+    return VS_OK;
+}
+
 }  // extern "C"

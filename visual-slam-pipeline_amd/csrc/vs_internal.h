@@ -136,6 +136,8 @@ struct vs_ctx {
     vs::DevBuf em_sync;  // k_emat's split-workgroup meeting area for the context's own calls (zeroed)
     vs::DevBuf fm_sync;  // k_fmat's (zeroed)
     vs::DevBuf tie_totals;  // NMS tie accounting since the last reset: {frames, frames with a tie, window, cut, order}
+    vs::DevBuf cloud;  // the cloud filter's partial k-NN lists, stage buffers and flags (cloud.hip), sized on first use
+    int cloud_cus = 0;  // the device's CU count (k_cloud_knn's candidate split), read on first use
 
     bool prof_on = false;
     int prof_mode = 0;  // 1: every stage, 2: extraction stages only (vs_profile_enable)
@@ -311,6 +313,10 @@ int subset_table(int rows, int n_base, int iters, int* out, hipStream_t s);
 int emat_points(vs_ctx* ctx, int P, const float* d_p1, const float* d_p2, const int* d_off, const float* d_depth1,
                 const float* d_depth2, int h, int w, const double K[4], double* d_R, double* d_t, double* d_scale,
                 int* d_ok, int* d_diag, hipStream_t s);
+// The sparse-map cloud filter (cloud.hip; vs_cloud_filter_dev).  d_pre (optional): one byte per point,
+// 0 drops the point before the box clip (a tracker's validity flags); d_idx indexes the input.
+int cloud_filter(vs_ctx* ctx, const double* d_pts, int n, const uint8_t* d_pre, const vs_cloud_filter_config& c,
+                 double* d_out, int* d_idx, int* d_counts, hipStream_t s);
 // Local bundle adjustment over a gathered window (host arrays in/out, see vs_local_ba)
 int local_ba(vs_ctx* ctx, int N, double* R, double* t, int M, double* P, int n_obs, const int* okf, const int* opt,
              const double* ouv, const double K4[4], int max_iter, double* err_before, double* err_after, int stats[3]);

@@ -108,6 +108,11 @@ _SIG = {
     "vs_dense_points_dev": (_P, [_P]),
     "vs_dense_write_ply": (_I, [_P, ctypes.c_char_p]),
     "vs_slam_attach_dense": (_I, [_P, _P]),
+    "vs_cloud_filter_default_config": (None, [_P]),
+    "vs_cloud_knn_dev": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "vs_cloud_filter_dev": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
+    "vs_cloud_filter": (_I, [_P, _P, _I, _P, _P, _P, _P]),
+    "vs_slam_filtered_map": (_I, [_P, _I, _I, _P, _P, _P]),
     "vs_slam_loops": (_I, [_P, _I, _P, _P, _P, _P]),
     "vs_pose_graph_optimize": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, ctypes.c_double, _I, _P, _P]),
     "vs_pgo_transform_points": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P]),
@@ -499,6 +504,53 @@ class Context:
         _check(self.lib.vs_ransac_3d3d_pairs_dev(self.h, P, d_pairs, d_kps, cap, d_good, d_ngood, d_depth, h, w,
                                                  _ptr(Ka), d_seeds, iters, thr, d_R, d_t, d_ok, d_diag, stream))
 
+    # ---- the sparse-map cloud filter (main.cpp:512-642, 1185-1215, 1340-1368) ----
+    def cloud_config(self, **overrides):
+        """vs_cloud_filter_config with the reference's values; bbox=(min[3], max[3]) switches the clip on."""
+        cfg = CloudFilterConfig()
+        self.lib.vs_cloud_filter_default_config(ctypes.byref(cfg))
+        for k, v in overrides.items():
+            if k == "bbox":
+                cfg.use_bbox = 1
+                cfg.bbox_min[:] = [float(x) for x in v[0]]
+                cfg.bbox_max[:] = [float(x) for x in v[1]]
+            else:
+                setattr(cfg, k, v)
+        return cfg
+
+    def cloud_knn_dev(self, d_pts, n, k, d_nbr, d_d2, split=0, stream=None):
+        _check(self.lib.vs_cloud_knn_dev(self.h, d_pts, n, k, split, d_nbr, d_d2, stream))
+
+    def cloud_knn(self, pts, k, split=0):
+        """Exact k nearest neighbours of host points [n, 3] -> (nbr [n, k] i32, d2 [n, k] f64), ordered
+        by (d2, index).  Stages through torch device tensors (vs_cloud_knn_dev)."""
+        import torch
+        p = torch.from_numpy(np.ascontiguousarray(pts, np.float64).reshape(-1, 3)).cuda()
+        n = p.shape[0]
+        nbr = torch.empty((n, k), dtype=torch.int32, device=p.device)
+        d2 = torch.empty((n, k), dtype=torch.float64, device=p.device)
+        self.cloud_knn_dev(p.data_ptr(), n, k, nbr.data_ptr(), d2.data_ptr(), split,
+                           torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        return nbr.cpu().numpy(), d2.cpu().numpy()
+
+    def cloud_filter_dev(self, d_pts, n, cfg, d_out, d_idx, d_counts, stream=None):
+        """Device pointers; cfg a CloudFilterConfig or None (the reference's values).  Enqueue only."""
+        _check(self.lib.vs_cloud_filter_dev(self.h, d_pts, n, None if cfg is None else ctypes.byref(cfg), d_out,
+                                            d_idx, d_counts, stream))
+
+    def cloud_filter(self, pts, cfg=None):
+        """Host points [n, 3] -> (survivors [m, 3], their indices [m], counts [3] = after the box, after
+        statistical_outlier_removal, after surface_aware_filter)."""
+        p = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        n = p.shape[0]
+        out = np.zeros((max(n, 1), 3), np.float64)
+        idx = np.zeros(max(n, 1), np.int32)
+        counts = np.zeros(3, np.int32)
+        _check(self.lib.vs_cloud_filter(self.h, _ptr(p), n, None if cfg is None else ctypes.byref(cfg), _ptr(out),
+                                        _ptr(idx), _ptr(counts)))
+        return out[:counts[2]], idx[:counts[2]], counts
+
     # ---- profiling ----
     def spcf_write_dev(self, path, frame_idx, F, d_kps, d_desc, d_n, cap, append=False, stream=None):
         """vs_extract_batch_dev outputs (device pointers) -> SPCF entries frame_idx[f]."""
@@ -649,6 +701,16 @@ class Slam:
         _check(self.lib.vs_slam_map(self.h, m, _ptr(pos), _ptr(valid), ctypes.byref(n)))
         return pos[:m], valid[:m]
 
+    def filtered_map(self, valid_only=False):
+        """The cleaned sparse cloud the reference displays and saves (main.cpp:1340-1368 without
+        densify_surfaces): (points [m, 3], indices into map_points() [m])."""
+        n = ctypes.c_int(0)
+        cap = max(len(self.map_points()[1]), 1)
+        pts = np.zeros((cap, 3))
+        idx = np.zeros(cap, np.int32)
+        _check(self.lib.vs_slam_filtered_map(self.h, int(bool(valid_only)), cap, _ptr(pts), _ptr(idx), ctypes.byref(n)))
+        return pts[:n.value], idx[:n.value]
+
 
 def exported_symbols_from_header(header_path):
     """Function names declared in include/vslam_abi.h (for the export test)."""
@@ -706,6 +768,13 @@ def pose_graph_optimize(ctx, R, t, loops=(), gravity=None, height=0.0, iters=20)
                                           _ptr(ltv), _ptr(ls), None if g is None else _ptr(g), float(height), iters,
                                           _ptr(st), _ptr(ch)))
     return R, t, st, ch
+
+
+class CloudFilterConfig(ctypes.Structure):
+    """vs_cloud_filter_config (Context.cloud_config fills in the reference's values)."""
+    _fields_ = [("sor_k", ctypes.c_int), ("sor_std_ratio", ctypes.c_double), ("surf_k", ctypes.c_int),
+                ("surf_min_anisotropy", ctypes.c_double), ("use_bbox", ctypes.c_int),
+                ("bbox_min", ctypes.c_double * 3), ("bbox_max", ctypes.c_double * 3)]
 
 
 # ---- F4: dense voxel fusion (main.cpp:1081-1146) ----------------------------------------------
