@@ -533,6 +533,46 @@ int vs_cloud_filter(vs_ctx* ctx, const double* pts, int n, const vs_cloud_filter
  * to pts (x 3) and idx (indices into vs_slam_map's list), each nullable.  Synchronous. */
 int vs_slam_filtered_map(vs_slam* slam, int valid_only, int cap, double* pts, int* idx, int* n);
 
+/* ---- surface densification and normals (main.cpp:846-965 after the filter, :645-672, :1369-1387) ----
+ * estimate_normals: point i's list is i itself, then its min(k, n) - 1 nearest others by (d2, index);
+ * with fewer than 3 entries the normal is (0, 0, 1) (eigenvalues 0), otherwise the eigenvector of the
+ * smallest eigenvalue of the list's scatter matrix (centroid and scatter summed in list order).
+ * Eigenvector signs: the reference takes whatever Eigen's solver returns; here every eigenvector that
+ * is returned or used is oriented so that its component of largest magnitude is positive (equal
+ * magnitudes: the lowest index).  This is the one place where the result is defined here and not by
+ * the reference.
+ * densify_surfaces, restated literally (normals with k = 20; radius search d2 < r^2 ordered by
+ * (d2, index); coplanar list; plane fit; lattice by repeated addition; candidates dropped within
+ * sqrt(0.2) step of any input point or farther than sqrt(0.5) r from every coplanar point; one point
+ * per voxel of 0.7 step, the first inserted wins).  The reference lists the winners in an
+ * unordered_map's order; here they come out in insertion order: the surviving input points in input
+ * order, then the surviving filled points by (generating point, u step, v step).  n < 20 returns the
+ * input unchanged.  Deviation: a point with more than VS_DENSIFY_MAX_NEIGHBOURS points (itself
+ * included) inside the radius generates nothing and is counted.  A configuration with more than
+ * VS_DENSIFY_MAX_GRID lattice nodes per point ((floor(2 r / step) + 1)^2), or n (1 + nodes) above
+ * 2^24: VS_ERR_CAPACITY.  A cloud whose cells (|p| / r >= 2^20) or voxels (span >= 2^21) cannot be
+ * packed is reported on the device as d_counts[2] = -1 with nothing written; the host calls turn
+ * that into VS_ERR_CAPACITY.  One call per context at a time. */
+#define VS_DENSIFY_MAX_NEIGHBOURS 512
+#define VS_DENSIFY_MAX_GRID 256
+typedef struct vs_cloud_densify_config { double search_radius, fill_step, normal_thresh; } vs_cloud_densify_config; /* 0.12, 0.05, 0.95 */
+void vs_cloud_densify_default_config(vs_cloud_densify_config* cfg);
+/* Normals of n device points: d_normals [n][3], d_eig [n][3] descending (nullable).  1 <= k <=
+ * VS_CLOUD_MAX_K, n <= VS_CLOUD_MAX_POINTS (VS_ERR_CAPACITY).  Enqueue only. */
+int vs_cloud_normals_dev(vs_ctx* ctx, const double* d_pts, int n, int k, double* d_normals, double* d_eig, void* stream);
+/* The same on host buffers; synchronous. */
+int vs_cloud_normals(vs_ctx* ctx, const double* pts, int n, int k, double* normals, double* eig);
+/* d_out [cap][3], d_src [cap]: an input point that survives carries its input index, a filled point
+ * -(i + 1) with i the input point whose plane produced it.  d_counts [4] = {input points that
+ * survive, filled points that survive, their total, points skipped at the neighbour cap}; when the
+ * total exceeds cap the first cap entries are written and the total is still reported.  cfg NULL =
+ * the reference's values.  Enqueue only. */
+int vs_cloud_densify_dev(vs_ctx* ctx, const double* d_pts, int n, const vs_cloud_densify_config* cfg, int cap,
+                         double* d_out, int* d_src, int* d_counts, void* stream);
+/* The same on host buffers; synchronous. */
+int vs_cloud_densify(vs_ctx* ctx, const double* pts, int n, const vs_cloud_densify_config* cfg, int cap, double* out,
+                     int* src, int counts[4]);
+
 /* ---- F4: Optimizer::pose_graph_optimize (Optimizer.cpp:654-863), g2o LM restated -------------
  * N keyframe poses (camera -> world, R [N][9] row-major, t [N][3], keyframe order; the first is
  * fixed), odometry edges between consecutive keyframes from these poses, L loop constraints

@@ -2,6 +2,10 @@
 at the tracking tests' map sizes, with device events over repeated calls after warm-up.
 
     python tools/bench_cloud.py [--out profiles/cloud_filter.json] [--sizes 12000 60000] [--k 25]
+    python tools/bench_cloud.py --densify [--out profiles/cloud_densify.json]
+
+--densify times vs_cloud_normals_dev (k = 20) and vs_cloud_densify_dev with the same protocol on the same cloud with
+holes cut into the planes, and a second pass with the context's stage profile on gives each kernel's share.
 
 Pair tests per filter call = n0^2 + n1^2 (n0 points enter statistical_outlier_removal, n1 enter
 surface_aware_filter: every query meets every candidate).  One pair test is 3 sub, 3 mul, 2 add and
@@ -34,6 +38,43 @@ def cloud(n, seed=1):
     return rng.permutation(np.concatenate([a, b, blob, rng.uniform(-12, 12, (n_out, 3))]))
 
 
+def holed(p):
+    """The cloud without the points of a 0.5 m lattice of discs (radius 0.1 m) on either plane."""
+    def disc(u, v):
+        return np.hypot((u + 0.25) % 0.5 - 0.25, (v + 0.25) % 0.5 - 0.25) < 0.1
+    on_a, on_b = np.abs(p[:, 2]) < 0.02, np.abs(p[:, 0] - 4.5) < 0.02
+    return p[~((on_a & disc(p[:, 0], p[:, 1])) | (on_b & disc(p[:, 1], p[:, 2])))]
+
+
+def densify_runs(ctx, sizes, stream, dev):
+    s, runs = stream.cuda_stream, []
+    for n0 in sizes:
+        p = torch.from_numpy(np.ascontiguousarray(holed(cloud(n0)))).to(dev)
+        n, cap = p.shape[0], p.shape[0] * 26
+        nrm = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        out = torch.zeros((cap, 3), dtype=torch.float64, device=dev)
+        src = torch.zeros(cap, dtype=torch.int32, device=dev)
+        cnt = torch.zeros(4, dtype=torch.int32, device=dev)
+        reps = max(10, int(5e9 / (n * n)))
+        normals = lambda: ctx.cloud_normals_dev(p.data_ptr(), n, 20, nrm.data_ptr(), None, s)  # noqa: E731
+        densify = lambda: ctx.cloud_densify_dev(p.data_ptr(), n, None, cap, out.data_ptr(), src.data_ptr(),  # noqa: E731
+                                                cnt.data_ptr(), s)
+        n_ms, d_ms = timed(normals, stream, 5, reps), timed(densify, stream, 5, reps)
+        ctx.profile(True)  # a pass of its own: the stage events are not part of the timed calls above
+        ctx.profile_reset()
+        for _ in range(10):
+            densify()
+        torch.cuda.synchronize()
+        prof = ctx.profile_read()
+        ctx.profile(False)
+        tot = sum(ms for ms, _ in prof.values()) or 1.0
+        runs.append({"n_before_holes": n0, "n": n, "counts": cnt.cpu().numpy().tolist(), "reps_per_round": reps,
+                     "normals_ms_rounds": n_ms, "normals_ms": float(np.median(n_ms)),
+                     "densify_ms_rounds": d_ms, "densify_ms": float(np.median(d_ms)),
+                     "densify_kernel_share": {k: ms / tot for k, (ms, _) in prof.items()}})
+    return runs
+
+
 def timed(fn, stream, warm, reps, rounds=5):
     """ms per call: events on the stream the calls are enqueued on, around reps calls, per round."""
     for _ in range(warm):
@@ -56,6 +97,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", type=int, nargs="+", default=[12000, 60000])
     ap.add_argument("--k", type=int, default=25)
+    ap.add_argument("--densify", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     cus = torch.cuda.get_device_properties(0).multi_processor_count
@@ -63,37 +105,45 @@ def main():
     with vslam_abi.Context(0) as ctx:
         cfg = ctx.cloud_config(sor_k=args.k, surf_k=args.k)
         stream = torch.cuda.ExternalStream(ctx.stream)  # the context's own stream
-        s = stream.cuda_stream
-        for n in args.sizes:
-            p = torch.from_numpy(cloud(n)).to(dev)
-            out = torch.zeros((n, 3), dtype=torch.float64, device=dev)
-            idx = torch.zeros(n, dtype=torch.int32, device=dev)
-            cnt = torch.zeros(3, dtype=torch.int32, device=dev)
-            nbr = torch.zeros((n, args.k), dtype=torch.int32, device=dev)
-            d2 = torch.zeros((n, args.k), dtype=torch.float64, device=dev)
-            reps = max(10, int(2e10 / (n * n)))
-            f_ms = timed(lambda: ctx.cloud_filter_dev(p.data_ptr(), n, cfg, out.data_ptr(), idx.data_ptr(),
-                                                      cnt.data_ptr(), s), stream, 5, reps)
-            k_ms = timed(lambda: ctx.cloud_knn_dev(p.data_ptr(), n, args.k, nbr.data_ptr(), d2.data_ptr(), 0, s),
-                         stream, 5, reps)
-            c = cnt.cpu().numpy().tolist()
-            blocks = (n + 255) // 256
-            split = max(1, min(-(-cus // blocks), n // 512, 64))  # cloud.hip knn_split
-            pairs_f, pairs_k = float(c[0]) ** 2 + float(c[1]) ** 2, float(n) ** 2
-            run = {"n": n, "counts": c, "split": split, "reps_per_round": reps,
-                   "filter_ms_rounds": f_ms, "filter_ms": float(np.median(f_ms)),
-                   "knn_ms_rounds": k_ms, "knn_ms": float(np.median(k_ms))}
-            run["filter_pair_tests_per_s"] = pairs_f / (run["filter_ms"] * 1e-3)
-            run["knn_pair_tests_per_s"] = pairs_k / (run["knn_ms"] * 1e-3)
-            run["filter_share_of_fp64_valu_peak"] = run["filter_pair_tests_per_s"] * OPS_PER_PAIR / PEAK_FP64_OPS
-            run["knn_share_of_fp64_valu_peak"] = run["knn_pair_tests_per_s"] * OPS_PER_PAIR / PEAK_FP64_OPS
-            res["runs"].append(run)
+        if args.densify:
+            res = {"device": res["device"], "cus": cus, "runs": densify_runs(ctx, args.sizes, stream, dev)}
+        else:
+            res["runs"] = filter_runs(ctx, args, cfg, cus, stream, dev)
     line = json.dumps(res)
     print(line)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             f.write(line + "\n")
+
+
+def filter_runs(ctx, args, cfg, cus, stream, dev):
+    s, runs = stream.cuda_stream, []
+    for n in args.sizes:
+        p = torch.from_numpy(cloud(n)).to(dev)
+        out = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        idx = torch.zeros(n, dtype=torch.int32, device=dev)
+        cnt = torch.zeros(3, dtype=torch.int32, device=dev)
+        nbr = torch.zeros((n, args.k), dtype=torch.int32, device=dev)
+        d2 = torch.zeros((n, args.k), dtype=torch.float64, device=dev)
+        reps = max(10, int(2e10 / (n * n)))
+        f_ms = timed(lambda: ctx.cloud_filter_dev(p.data_ptr(), n, cfg, out.data_ptr(), idx.data_ptr(),
+                                                  cnt.data_ptr(), s), stream, 5, reps)
+        k_ms = timed(lambda: ctx.cloud_knn_dev(p.data_ptr(), n, args.k, nbr.data_ptr(), d2.data_ptr(), 0, s),
+                     stream, 5, reps)
+        c = cnt.cpu().numpy().tolist()
+        blocks = (n + 255) // 256
+        split = max(1, min(-(-cus // blocks), n // 512, 64))  # cloud.hip knn_split
+        pairs_f, pairs_k = float(c[0]) ** 2 + float(c[1]) ** 2, float(n) ** 2
+        run = {"n": n, "counts": c, "split": split, "reps_per_round": reps,
+               "filter_ms_rounds": f_ms, "filter_ms": float(np.median(f_ms)),
+               "knn_ms_rounds": k_ms, "knn_ms": float(np.median(k_ms))}
+        run["filter_pair_tests_per_s"] = pairs_f / (run["filter_ms"] * 1e-3)
+        run["knn_pair_tests_per_s"] = pairs_k / (run["knn_ms"] * 1e-3)
+        run["filter_share_of_fp64_valu_peak"] = run["filter_pair_tests_per_s"] * OPS_PER_PAIR / PEAK_FP64_OPS
+        run["knn_share_of_fp64_valu_peak"] = run["knn_pair_tests_per_s"] * OPS_PER_PAIR / PEAK_FP64_OPS
+        runs.append(run)
+    return runs
 
 
 if __name__ == "__main__":

@@ -40,18 +40,13 @@
 
 namespace vs {
 
-constexpr int kKnnLanes = 256;   // queries per workgroup
 constexpr int kKnnTile = 1024;   // candidates per LDS tile
 constexpr int kKnnGroup = 8;     // candidates tested per loop trip (a power of two)
 constexpr int kKnnPend = 12;     // pending candidates per lane (> kKnnGroup: a group may append that many)
-constexpr int kKnnMaxSplit = 64; // workgroups per query block
 constexpr int kKnnMinChunk = 512;  // automatic split: at least this many candidates per workgroup
 constexpr int kCompact = 1024;   // points per compaction block
-constexpr int kNoIdx = INT_MAX;  // an empty list slot (d2 = +inf)
 
 enum { kReduceKnn = 0, kReduceMean = 1, kReduceSurface = 2 };
-
-__device__ __forceinline__ int dev_count(const int* d_n, int n_max) { return d_n ? min(*d_n, n_max) : n_max; }
 
 // The lane's sorted list and its pending candidates in LDS, both [slot][lane].  A candidate below the
 // lane's k-th distance is only appended to the pending slots (one write); the wave inserts every
@@ -359,10 +354,6 @@ __global__ __launch_bounds__(kCompact) void k_cloud_compact(const double* __rest
     if (tid == 0 && first + kCompact >= n) *d_n_out = total;  // the block that holds the last point (or block 0)
 }
 
-namespace {
-
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // workgroups per query block: enough for blocks x S to cover the CUs, chunks of >= kKnnMinChunk candidates
 int knn_split(vs_ctx* ctx, int n, int forced) {
     if (forced > 0) return std::min(forced, kKnnMaxSplit);
@@ -377,13 +368,7 @@ int knn_split(vs_ctx* ctx, int n, int forced) {
     return std::max(1, std::min({want, n / kKnnMinChunk, kKnnMaxSplit}));
 }
 
-// The context's scratch for clouds of up to n points, k neighbours and S partial lists.
-struct CloudScratch {
-    double *part_d2, *mean, *pts_a, *pts_b;
-    int *part_idx, *idx_a, *idx_b;
-    uint8_t* flags;
-};
-
+// The context's scratch for clouds of up to n points, k neighbours and S partial lists (vs_internal.h).
 int cloud_scratch(vs_ctx* ctx, int n, int k, int S, CloudScratch* cs) {
     const size_t nk = (size_t)std::max(S, 1) * std::max(k, 1) * n;
     const size_t b_d2 = up256(nk * sizeof(double)), b_idx = up256(nk * sizeof(int));
@@ -407,6 +392,8 @@ void launch_knn(const CloudScratch& cs, const double* d_pts, const int* d_n, int
     hipLaunchKernelGGL(k_cloud_knn, dim3((n_max + kKnnLanes - 1) / kKnnLanes, S), dim3(kKnnLanes), 0, s, d_pts, d_n,
                        n_max, k, skip_small, cs.part_d2, cs.part_idx);
 }
+
+namespace {
 
 void launch_compact(const double* in, const int* idx_in, const uint8_t* flags, const int* d_n_in, int n_max,
                     double* out, int* idx_out, int* d_n_out, hipStream_t s) {

@@ -113,6 +113,11 @@ _SIG = {
     "vs_cloud_filter_dev": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
     "vs_cloud_filter": (_I, [_P, _P, _I, _P, _P, _P, _P]),
     "vs_slam_filtered_map": (_I, [_P, _I, _I, _P, _P, _P]),
+    "vs_cloud_densify_default_config": (None, [_P]),
+    "vs_cloud_normals_dev": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "vs_cloud_normals": (_I, [_P, _P, _I, _I, _P, _P]),
+    "vs_cloud_densify_dev": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _P]),
+    "vs_cloud_densify": (_I, [_P, _P, _I, _P, _I, _P, _P, _P]),
     "vs_slam_loops": (_I, [_P, _I, _P, _P, _P, _P]),
     "vs_pose_graph_optimize": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, ctypes.c_double, _I, _P, _P]),
     "vs_pgo_transform_points": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P]),
@@ -551,6 +556,51 @@ class Context:
                                         _ptr(idx), _ptr(counts)))
         return out[:counts[2]], idx[:counts[2]], counts
 
+    # ---- surface densification and normals (main.cpp:645-672, 846-965) ----
+    def densify_config(self, **overrides):
+        """vs_cloud_densify_config with the reference's values (0.12, 0.05, 0.95)."""
+        cfg = CloudDensifyConfig()
+        self.lib.vs_cloud_densify_default_config(ctypes.byref(cfg))
+        for k, v in overrides.items():
+            setattr(cfg, k, v)
+        return cfg
+
+    def cloud_normals_dev(self, d_pts, n, k, d_normals, d_eig=None, stream=None):
+        _check(self.lib.vs_cloud_normals_dev(self.h, d_pts, n, k, d_normals, d_eig, stream))
+
+    def cloud_normals(self, pts, k=20):
+        """Host points [n, 3] -> (normals [n, 3], eigenvalues [n, 3] descending); the largest component of
+        every normal is positive."""
+        p = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        n = p.shape[0]
+        normals, eig = np.zeros((max(n, 1), 3)), np.zeros((max(n, 1), 3))
+        _check(self.lib.vs_cloud_normals(self.h, _ptr(p), n, k, _ptr(normals), _ptr(eig)))
+        return normals[:n], eig[:n]
+
+    def cloud_densify_dev(self, d_pts, n, cfg, cap, d_out, d_src, d_counts, stream=None):
+        """Device pointers; cfg a CloudDensifyConfig or None (the reference's values).  Enqueue only."""
+        _check(self.lib.vs_cloud_densify_dev(self.h, d_pts, n, None if cfg is None else ctypes.byref(cfg), cap, d_out,
+                                             d_src, d_counts, stream))
+
+    def cloud_densify(self, pts, cfg=None, cap=None):
+        """Host points [n, 3] -> (points [min(cap, total), 3], src, counts [4] = surviving input points,
+        surviving filled points, total, points skipped at the neighbour cap).  src: the input index of a
+        surviving input point, -(i + 1) for a point filled from input point i's plane.  cap None: room for
+        every lattice node."""
+        p = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        n = p.shape[0]
+        if cap is None:
+            c = cfg if cfg is not None else self.densify_config()
+            per_axis = int(np.floor(2.0 * c.search_radius / c.fill_step)) + 1 if c.fill_step > 0 else 1
+            cap = n * (1 + min(per_axis * per_axis, 256))
+        out = np.zeros((max(cap, 1), 3), np.float64)
+        src = np.zeros(max(cap, 1), np.int32)
+        counts = np.zeros(4, np.int32)
+        _check(self.lib.vs_cloud_densify(self.h, _ptr(p), n, None if cfg is None else ctypes.byref(cfg), cap, _ptr(out),
+                                         _ptr(src), _ptr(counts)))
+        m = min(cap, int(counts[2]))
+        return out[:m], src[:m], counts
+
     # ---- profiling ----
     def spcf_write_dev(self, path, frame_idx, F, d_kps, d_desc, d_n, cap, append=False, stream=None):
         """vs_extract_batch_dev outputs (device pointers) -> SPCF entries frame_idx[f]."""
@@ -775,6 +825,11 @@ class CloudFilterConfig(ctypes.Structure):
     _fields_ = [("sor_k", ctypes.c_int), ("sor_std_ratio", ctypes.c_double), ("surf_k", ctypes.c_int),
                 ("surf_min_anisotropy", ctypes.c_double), ("use_bbox", ctypes.c_int),
                 ("bbox_min", ctypes.c_double * 3), ("bbox_max", ctypes.c_double * 3)]
+
+
+class CloudDensifyConfig(ctypes.Structure):
+    """vs_cloud_densify_config (Context.densify_config fills in the reference's values)."""
+    _fields_ = [("search_radius", ctypes.c_double), ("fill_step", ctypes.c_double), ("normal_thresh", ctypes.c_double)]
 
 
 # ---- F4: dense voxel fusion (main.cpp:1081-1146) ----------------------------------------------
