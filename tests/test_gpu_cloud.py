@@ -116,6 +116,20 @@ def test_knn_ties_take_the_lowest_index(vsctx, split):
     assert np.array_equal(nbr, rn)
 
 
+@pytest.mark.parametrize("split", [0, 3])
+def test_knn_empty_slots(vsctx, split):
+    """k above n - 1: the partial lists end in empty slots, which the merge hands on as (-1, +inf)."""
+    p = np.random.default_rng(10).uniform(0, 4, (10, 3))
+    nbr, d2 = vsctx.cloud_knn(p, 25, split)
+    rn, rd = ref_knn(p, 9)
+    assert np.array_equal(d2[:, :9].view(np.uint64), rd.view(np.uint64))
+    assert np.array_equal(nbr[:, :9], rn)
+    assert np.all(nbr[:, 9:] == -1) and np.all(np.isposinf(d2[:, 9:]))
+    nbr, d2 = vsctx.cloud_knn(p[:1], 25, split)  # every slot empty
+    assert nbr.shape == d2.shape == (1, 25)
+    assert np.all(nbr == -1) and np.all(np.isposinf(d2))
+
+
 CASES = {"default": {}, "box": dict(bbox=([-0.5, -0.5, -0.5], [2.5, 1.2, 2.5])), "no_sor": dict(sor_k=0),
          "no_surface": dict(surf_k=0)}
 

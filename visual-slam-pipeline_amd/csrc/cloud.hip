@@ -17,7 +17,9 @@
 //                      a small cloud still covers the CUs; each writes its partial list to [S][k][N].
 //   k_cloud_reduce     one point per lane: merges the S partial lists by (d2, index) and computes the
 //                      mean neighbour distance (stage A), the scatter matrix's eigenvalues and the
-//                      keep flag (stage B), or writes the merged list (vs_cloud_knn_dev).
+//                      keep flag (stage B), or writes the merged list (vs_cloud_knn_dev).  The merge, the
+//                      scatter and eigen-solve, the compaction's block rank and the scratch carving are
+//                      cloud_common.h's knn_merge, scatter_eig, block_rank and Carver, shared with densify.hip.
 //   k_cloud_threshold  one workgroup: mean and population variance of the mean distances in a fixed
 //                      order, threshold = mean + std_ratio * std, keep flags.
 //   k_cloud_box        keep flags of the inclusive box clip (and of a caller's validity bytes).
@@ -35,8 +37,7 @@
 #include <cstring>
 
 #include "block_reduce.h"
-#include "pnp_solvers.h"
-#include "vs_internal.h"
+#include "cloud_common.h"
 
 namespace vs {
 
@@ -201,62 +202,23 @@ __global__ __launch_bounds__(kKnnLanes) void k_cloud_reduce(ReduceArgs a) {
         if (a.mode == kReduceSurface) a.flags[q] = 1;
         return;
     }
-    for (int s = 0; s < S; s++) s_cur[s * kKnnLanes + tid] = 0;
-    const size_t nm = (size_t)a.n_max, list = (size_t)k * nm;
     double sum = 0;
-    for (int t = 0; t < k; t++) {
-        // the smallest head of the S lists by (d2, index); a consumed list (cursor k) is skipped
-        double bd = INFINITY;
-        int bi = kNoIdx, bs = 0;
-        for (int s = 0; s < S; s++) {
-            const int c = s_cur[s * kKnnLanes + tid];
-            if (c >= k) continue;
-            const size_t at = (size_t)s * list + (size_t)c * nm + q;
-            const double d = a.part_d2[at];
-            const int i = a.part_idx[at];
-            if (d < bd || (d == bd && i < bi)) {
-                bd = d;
-                bi = i;
-                bs = s;
-            }
-        }
-        s_cur[bs * kKnnLanes + tid]++;
+    knn_merge(a.part_d2, a.part_idx, S, k, a.n_max, q, s_cur + tid, k, [&](int t, double d2, int idx) {
         if (a.mode == kReduceKnn) {
-            a.out_d2[(size_t)q * k + t] = bd;
-            a.out_nbr[(size_t)q * k + t] = bi == kNoIdx ? -1 : bi;
+            a.out_d2[(size_t)q * k + t] = d2;
+            a.out_nbr[(size_t)q * k + t] = idx == kNoIdx ? -1 : idx;
         } else if (a.mode == kReduceMean) {
-            sum += sqrt(bd);  // main.cpp:536, ascending
+            sum += sqrt(d2);  // main.cpp:536, ascending
         } else {
-            s_nbr[t * kKnnLanes + tid] = bi == kNoIdx ? q : bi;  // only with non-finite coordinates
+            s_nbr[t * kKnnLanes + tid] = idx == kNoIdx ? q : idx;  // only with non-finite coordinates
         }
-    }
+    });
     if (a.mode == kReduceMean) {
         a.mean[q] = sum / k;  // main.cpp:540
     } else if (a.mode == kReduceSurface) {
         // main.cpp:589-631: centroid, scatter summed in neighbour order, eigenvalues, anisotropy
-        double cx = 0, cy = 0, cz = 0;
-        for (int t = 0; t < k; t++) {
-            const double* p = a.pts + 3 * (size_t)s_nbr[t * kKnnLanes + tid];
-            cx += p[0];
-            cy += p[1];
-            cz += p[2];
-        }
-        cx /= k;
-        cy /= k;
-        cz /= k;
-        double c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
-        for (int t = 0; t < k; t++) {
-            const double* p = a.pts + 3 * (size_t)s_nbr[t * kKnnLanes + tid];
-            const double dx = p[0] - cx, dy = p[1] - cy, dz = p[2] - cz;
-            c00 += dx * dx;
-            c01 += dx * dy;
-            c02 += dx * dz;
-            c11 += dy * dy;
-            c12 += dy * dz;
-            c22 += dz * dz;
-        }
-        double A[9] = {c00, c01, c02, c01, c11, c12, c02, c12, c22}, w[3], V[9];
-        vs_pnp::sym_eig_static<3>(A, w, V);  // sym_eig<3>'s rotations and results, indices static
+        double w[3], V[9];
+        scatter_eig(a.pts, s_nbr + tid, k, w, V);
         const double l1 = w[0], l3 = w[2];
         a.flags[q] = !(l1 < 1e-12) && 1.0 - l3 / l1 >= a.min_anisotropy;
     }
@@ -337,21 +299,15 @@ __global__ __launch_bounds__(kCompact) void k_cloud_compact(const double* __rest
         before = first;
     }
     const bool keep = i < n && (flags ? flags[i] != 0 : true);
-    const unsigned long long bal = __ballot(keep);
-    if (lane == 0) s_w[wv] = __popcll(bal);
-    __syncthreads();
-    int rank = before + __popcll(bal & ((1ull << lane) - 1ull)), total = before;
-    for (int w = 0; w < 16; w++) {
-        if (w < wv) rank += s_w[w];
-        total += s_w[w];
-    }
+    int total;
+    const int rank = before + block_rank(keep, s_w, total);
     if (keep) {
         out[3 * (size_t)rank] = in[3 * (size_t)i];
         out[3 * (size_t)rank + 1] = in[3 * (size_t)i + 1];
         out[3 * (size_t)rank + 2] = in[3 * (size_t)i + 2];
         idx_out[rank] = idx_in ? idx_in[i] : i;
     }
-    if (tid == 0 && first + kCompact >= n) *d_n_out = total;  // the block that holds the last point (or block 0)
+    if (tid == 0 && first + kCompact >= n) *d_n_out = before + total;  // the block of the last point (or block 0)
 }
 
 // workgroups per query block: enough for blocks x S to cover the CUs, chunks of >= kKnnMinChunk candidates
@@ -368,23 +324,26 @@ int knn_split(vs_ctx* ctx, int n, int forced) {
     return std::max(1, std::min({want, n / kKnnMinChunk, kKnnMaxSplit}));
 }
 
-// The context's scratch for clouds of up to n points, k neighbours and S partial lists (vs_internal.h).
+// The context's scratch for clouds of up to n points, k neighbours and S partial lists (cloud_common.h).
 int cloud_scratch(vs_ctx* ctx, int n, int k, int S, CloudScratch* cs) {
     const size_t nk = (size_t)std::max(S, 1) * std::max(k, 1) * n;
-    const size_t b_d2 = up256(nk * sizeof(double)), b_idx = up256(nk * sizeof(int));
-    const size_t b_p = up256((size_t)n * 3 * sizeof(double)), b_i = up256((size_t)n * sizeof(int));
-    const size_t b_m = up256((size_t)n * sizeof(double)), b_f = up256((size_t)n + kCompact);
-    VS_CHECK(ctx->cloud.ensure(b_d2 + b_idx + 2 * b_p + 2 * b_i + b_m + b_f));
-    char* p = ctx->cloud.as<char>();
-    cs->part_d2 = reinterpret_cast<double*>(p);
-    cs->part_idx = reinterpret_cast<int*>(p += b_d2);
-    cs->pts_a = reinterpret_cast<double*>(p += b_idx);
-    cs->pts_b = reinterpret_cast<double*>(p += b_p);
-    cs->idx_a = reinterpret_cast<int*>(p += b_p);
-    cs->idx_b = reinterpret_cast<int*>(p += b_i);
-    cs->mean = reinterpret_cast<double*>(p += b_i);
-    cs->flags = reinterpret_cast<uint8_t*>(p += b_m);
-    return VS_OK;
+    return carve_buf(ctx->cloud, [&](Carver& c) {
+        cs->part_d2 = c.take<double>(nk);
+        cs->part_idx = c.take<int>(nk);
+        cs->pts_a = c.take<double>((size_t)n * 3);
+        cs->pts_b = c.take<double>((size_t)n * 3);
+        cs->idx_a = c.take<int>(n);
+        cs->idx_b = c.take<int>(n);
+        cs->mean = c.take<double>(n);
+        cs->flags = c.take<uint8_t>((size_t)n + kCompact);  // k_cloud_compact reads whole 16-byte words below n
+    });
+}
+
+int cloud_size_check(const char* who, int n, int k) {
+    if (n <= VS_CLOUD_MAX_POINTS && k <= VS_CLOUD_MAX_K) return VS_OK;
+    set_error(std::string(who) + (n > VS_CLOUD_MAX_POINTS ? ": more than VS_CLOUD_MAX_POINTS points"
+                                                          : ": more than VS_CLOUD_MAX_K neighbours"));
+    return VS_ERR_CAPACITY;
 }
 
 void launch_knn(const CloudScratch& cs, const double* d_pts, const int* d_n, int n_max, int k, int S, int skip_small,
@@ -401,27 +360,14 @@ void launch_compact(const double* in, const int* idx_in, const uint8_t* flags, c
                        idx_in, flags, d_n_in, n_max, out, idx_out, d_n_out);
 }
 
-int check_config(const vs_cloud_filter_config& c, const char* who) {
-    if (c.sor_k < 0 || c.surf_k < 0) {
-        set_error(std::string(who) + ": negative neighbour count");
-        return VS_ERR_ARG;
-    }
-    if (c.sor_k > VS_CLOUD_MAX_K || c.surf_k > VS_CLOUD_MAX_K) {
-        set_error(std::string(who) + ": more than VS_CLOUD_MAX_K neighbours");
-        return VS_ERR_CAPACITY;
-    }
-    return VS_OK;
+int filter_check(const vs_cloud_filter_config& c, int n) {
+    VS_ARG(c.sor_k >= 0 && c.surf_k >= 0, "vs_cloud_filter: negative neighbour count");
+    return cloud_size_check("vs_cloud_filter", n, std::max(c.sor_k, c.surf_k));
 }
 
-}  // namespace
-
-int cloud_filter(vs_ctx* ctx, const double* d_pts, int n, const uint8_t* d_pre, const vs_cloud_filter_config& c,
-                 double* d_out, int* d_idx, int* d_counts, hipStream_t s) {
-    VS_CHECK(check_config(c, "vs_cloud_filter"));
-    if (n > VS_CLOUD_MAX_POINTS) {
-        set_error("vs_cloud_filter: more than VS_CLOUD_MAX_POINTS points");
-        return VS_ERR_CAPACITY;
-    }
+// the launches of cloud_filter; the caller has run filter_check
+int filter_enqueue(vs_ctx* ctx, const double* d_pts, int n, const uint8_t* d_pre, const vs_cloud_filter_config& c,
+                   double* d_out, int* d_idx, int* d_counts, hipStream_t s) {
     const int S = n > 0 ? knn_split(ctx, n, 0) : 1;
     CloudScratch cs;
     VS_CHECK(cloud_scratch(ctx, std::max(n, 1), std::max(c.sor_k, c.surf_k), S, &cs));
@@ -459,6 +405,14 @@ int cloud_filter(vs_ctx* ctx, const double* d_pts, int n, const uint8_t* d_pre, 
     return VS_OK;
 }
 
+}  // namespace
+
+int cloud_filter(vs_ctx* ctx, const double* d_pts, int n, const uint8_t* d_pre, const vs_cloud_filter_config& c,
+                 double* d_out, int* d_idx, int* d_counts, hipStream_t s) {
+    VS_CHECK(filter_check(c, n));
+    return filter_enqueue(ctx, d_pts, n, d_pre, c, d_out, d_idx, d_counts, s);
+}
+
 }  // namespace vs
 
 using namespace vs;
@@ -478,10 +432,7 @@ int vs_cloud_knn_dev(vs_ctx* ctx, const double* d_pts, int n, int k, int split, 
                      void* stream) {
     VS_ARG(ctx && d_pts && d_nbr && d_d2, "vs_cloud_knn_dev: null argument");
     VS_ARG(n >= 0 && k >= 1 && split >= 0 && split <= kKnnMaxSplit, "vs_cloud_knn_dev: bad size");
-    if (n > VS_CLOUD_MAX_POINTS || k > VS_CLOUD_MAX_K) {
-        set_error("vs_cloud_knn_dev: more than VS_CLOUD_MAX_POINTS points or VS_CLOUD_MAX_K neighbours");
-        return VS_ERR_CAPACITY;
-    }
+    VS_CHECK(cloud_size_check("vs_cloud_knn_dev", n, k));
     if (n == 0) return VS_OK;
     VS_HIP(hipSetDevice(ctx->device));
     const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
@@ -499,32 +450,29 @@ int vs_cloud_knn_dev(vs_ctx* ctx, const double* d_pts, int n, int k, int split, 
 int vs_cloud_filter_dev(vs_ctx* ctx, const double* d_pts, int n, const vs_cloud_filter_config* cfg, double* d_out,
                         int* d_idx, int* d_counts, void* stream) {
     VS_ARG(ctx && d_out && d_idx && d_counts && n >= 0 && (n == 0 || d_pts), "vs_cloud_filter_dev: null argument");
-    vs_cloud_filter_config c;
-    if (cfg)
-        c = *cfg;
-    else
-        vs_cloud_filter_default_config(&c);
     VS_HIP(hipSetDevice(ctx->device));
-    return cloud_filter(ctx, d_pts, n, nullptr, c, d_out, d_idx, d_counts, stream ? (hipStream_t)stream : ctx->stream);
+    return cloud_filter(ctx, d_pts, n, nullptr, config_or(cfg, vs_cloud_filter_default_config), d_out, d_idx, d_counts,
+                        stream ? (hipStream_t)stream : ctx->stream);
 }
 
 int vs_cloud_filter(vs_ctx* ctx, const double* pts, int n, const vs_cloud_filter_config* cfg, double* out, int* idx,
                     int counts[3]) {
     VS_ARG(ctx && out && idx && counts && n >= 0 && (n == 0 || pts), "vs_cloud_filter: null argument");
-    if (n > VS_CLOUD_MAX_POINTS) {
-        set_error("vs_cloud_filter: more than VS_CLOUD_MAX_POINTS points");
-        return VS_ERR_CAPACITY;
-    }
+    const vs_cloud_filter_config c = config_or(cfg, vs_cloud_filter_default_config);
+    VS_CHECK(filter_check(c, n));  // before the staging is sized by n
     VS_HIP(hipSetDevice(ctx->device));
     const hipStream_t s = ctx->stream;
-    const size_t pb = up256((size_t)std::max(n, 1) * 3 * sizeof(double)), ib = up256((size_t)std::max(n, 1) * sizeof(int));
-    VS_CHECK(ctx->h_aux0.ensure(2 * pb + ib + 3 * sizeof(int)));
-    double* d_in = ctx->h_aux0.as<double>();
-    double* d_out = reinterpret_cast<double*>(ctx->h_aux0.as<char>() + pb);
-    int* d_idx = reinterpret_cast<int*>(ctx->h_aux0.as<char>() + 2 * pb);
-    int* d_counts = reinterpret_cast<int*>(ctx->h_aux0.as<char>() + 2 * pb + ib);
+    const size_t cnt = (size_t)std::max(n, 1);
+    double *d_in, *d_out;
+    int *d_idx, *d_counts;
+    VS_CHECK(carve_buf(ctx->h_aux0, [&](Carver& h) {
+        d_in = h.take<double>(cnt * 3);
+        d_out = h.take<double>(cnt * 3);
+        d_idx = h.take<int>(cnt);
+        d_counts = h.take<int>(3);
+    }));
     if (n > 0) VS_HIP(hipMemcpyAsync(d_in, pts, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    VS_CHECK(vs_cloud_filter_dev(ctx, d_in, n, cfg, d_out, d_idx, d_counts, s));
+    VS_CHECK(filter_enqueue(ctx, d_in, n, nullptr, c, d_out, d_idx, d_counts, s));
     VS_HIP(hipMemcpyAsync(counts, d_counts, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
     VS_HIP(hipStreamSynchronize(s));
     const int m = counts[2];

@@ -3,9 +3,9 @@
 // PLY (:1369-1387).  All arithmetic is fp64 in the reference's order, compiled without contraction.
 //
 // Normals: cloud.hip's exact brute-force search gives every point its k - 1 nearest others by (d2, index);
-//   k_cloud_normals  one point per lane: merges the S partial lists as k_cloud_reduce does, sums the centroid and
-//                    the scatter matrix in list order (the point itself first) and takes the eigenvector of the
-//                    smallest eigenvalue from sym_eig_static<3>.
+//   k_cloud_normals  one point per lane: merges the S partial lists (knn_merge), sums the centroid and the scatter
+//                    matrix in list order, the point itself first, and takes the eigenvector of the smallest
+//                    eigenvalue (scatter_eig; these, block_rank and Carver come from cloud_common.h).
 // Densification: the radius search runs on a uniform cell grid in HBM (edge = radius (1 + 2^-20), so a neighbour
 // inside the radius sits in one of the 27 surrounding cells whatever the rounding of the cell index).  The grid is
 // a counting sort of the points by the hash of their packed cell coordinates (21 bits per axis) into a power-of-two
@@ -42,8 +42,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "pnp_solvers.h"
-#include "vs_internal.h"
+#include "cloud_common.h"
 
 namespace vs {
 
@@ -92,51 +91,12 @@ __global__ __launch_bounds__(kKnnLanes) void k_cloud_normals(NormalArgs a) {
     const int found = min(a.k, n);  // the reference's query returns the point itself as well
     double nx = 0, ny = 0, nz = 1, w[3] = {0, 0, 0};  // main.cpp:655
     if (found >= 3) {
-        const int S = a.S, kk = a.k - 1;
-        const size_t nm = (size_t)a.n_max, list = (size_t)kk * nm;
-        for (int s = 0; s < S; s++) s_cur[s * kKnnLanes + tid] = 0;
         s_nbr[tid] = q;
-        for (int t = 1; t < found; t++) {
-            double bd = INFINITY;
-            int bi = kNoIdx, bs = 0;
-            for (int s = 0; s < S; s++) {
-                const int c = s_cur[s * kKnnLanes + tid];
-                if (c >= kk) continue;
-                const size_t at = (size_t)s * list + (size_t)c * nm + q;
-                const double d = a.part_d2[at];
-                const int i = a.part_idx[at];
-                if (d < bd || (d == bd && i < bi)) {
-                    bd = d;
-                    bi = i;
-                    bs = s;
-                }
-            }
-            s_cur[bs * kKnnLanes + tid]++;
-            s_nbr[t * kKnnLanes + tid] = bi == kNoIdx ? q : bi;  // only with non-finite coordinates
-        }
-        double cx = 0, cy = 0, cz = 0;
-        for (int t = 0; t < found; t++) {
-            const double* p = a.pts + 3 * (size_t)s_nbr[t * kKnnLanes + tid];
-            cx += p[0];
-            cy += p[1];
-            cz += p[2];
-        }
-        cx /= (double)found;
-        cy /= (double)found;
-        cz /= (double)found;
-        double c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
-        for (int t = 0; t < found; t++) {
-            const double* p = a.pts + 3 * (size_t)s_nbr[t * kKnnLanes + tid];
-            const double dx = p[0] - cx, dy = p[1] - cy, dz = p[2] - cz;
-            c00 += dx * dx;
-            c01 += dx * dy;
-            c02 += dx * dz;
-            c11 += dy * dy;
-            c12 += dy * dz;
-            c22 += dz * dz;
-        }
-        double A[9] = {c00, c01, c02, c01, c11, c12, c02, c12, c22}, V[9];
-        vs_pnp::sym_eig_static<3>(A, w, V);
+        knn_merge(a.part_d2, a.part_idx, a.S, a.k - 1, a.n_max, q, s_cur + tid, found - 1, [&](int t, double, int idx) {
+            s_nbr[(t + 1) * kKnnLanes + tid] = idx == kNoIdx ? q : idx;  // only with non-finite coordinates
+        });
+        double V[9];
+        scatter_eig(a.pts, s_nbr + tid, found, w, V);
         nx = V[2], ny = V[5], nz = V[8];  // the smallest eigenvalue's column
         orient(nx, ny, nz);
     }
@@ -181,6 +141,8 @@ struct Dz {
     int* counts;
 };
 
+// One loop over the voxel table's slots clears the shorter arrays too: T + 1 <= slots (T <= max(1024, 2 n) and
+// slots >= 2 (n_pad + n G) with n_pad >= 1024, G >= 1), which cloud_densify checks, and kStWords <= slots.
 __global__ __launch_bounds__(256) void k_dz_init(Dz a) {
     const size_t slots = (size_t)a.slot_mask + 1, stride = (size_t)gridDim.x * 256;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < slots; i += stride) {
@@ -416,19 +378,12 @@ __global__ __launch_bounds__(64) void k_dz_plane(Dz a) {
     double sx = 0, sy = 0, sz = 0;
     for (int t = lane; t < m; t += 64) sx += s_x[t], sy += s_y[t], sz += s_z[t];
     const double cx = wave_sum(sx) / (double)m, cy = wave_sum(sy) / (double)m, cz = wave_sum(sz) / (double)m;
-    double c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
-    for (int t = lane; t < m; t += 64) {
-        const double dx = s_x[t] - cx, dy = s_y[t] - cy, dz = s_z[t] - cz;
-        c00 += dx * dx;
-        c01 += dx * dy;
-        c02 += dx * dz;
-        c11 += dy * dy;
-        c12 += dy * dz;
-        c22 += dz * dz;
-    }
-    c00 = wave_sum(c00), c01 = wave_sum(c01), c02 = wave_sum(c02);
-    c11 = wave_sum(c11), c12 = wave_sum(c12), c22 = wave_sum(c22);
-    double A[9] = {c00, c01, c02, c01, c11, c12, c02, c12, c22}, w[3], V[9];
+    Scatter3 sc;
+    for (int t = lane; t < m; t += 64) sc.add(s_x[t] - cx, s_y[t] - cy, s_z[t] - cz);
+    sc.c00 = wave_sum(sc.c00), sc.c01 = wave_sum(sc.c01), sc.c02 = wave_sum(sc.c02);
+    sc.c11 = wave_sum(sc.c11), sc.c12 = wave_sum(sc.c12), sc.c22 = wave_sum(sc.c22);
+    double A[9], w[3], V[9];
+    sc.fill(A);
     vs_pnp::sym_eig_static<3>(A, w, V);
     const double l1 = w[0], l3 = w[2];
     if (l1 < 1e-12 || l3 / l1 > 0.15) return;
@@ -517,21 +472,14 @@ __device__ __forceinline__ bool dz_wins(const Dz& a, int n, int e) {
 __global__ __launch_bounds__(kBlk) void k_dz_count(Dz a) {
     __shared__ int s_w[16];
     const int n = a.n_max, tid = threadIdx.x, e = blockIdx.x * kBlk + tid;
-    const bool win = !a.state[kStErr] && dz_wins(a, n, e);
-    const unsigned long long bal = __ballot(win);
-    if ((tid & 63) == 0) s_w[tid >> 6] = __popcll(bal);
-    __syncthreads();
-    if (tid == 0) {
-        int t = 0;
-        for (int w = 0; w < 16; w++) t += s_w[w];
-        a.bsum[blockIdx.x] = t;
-    }
+    int total;
+    block_rank(!a.state[kStErr] && dz_wins(a, n, e), s_w, total);
+    if (tid == 0) a.bsum[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(kBlk) void k_dz_emit(Dz a) {
     __shared__ int s_w[16];
-    const int n = a.n_max, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int e = blockIdx.x * kBlk + tid;
+    const int n = a.n_max, tid = threadIdx.x, e = blockIdx.x * kBlk + tid;
     const bool err = a.state[kStErr] != 0;
     if (blockIdx.x == 0 && tid == 0) {
         const int kept = a.bsum[a.n_pad / kBlk], total = a.bsum[a.nblk];
@@ -542,11 +490,8 @@ __global__ __launch_bounds__(kBlk) void k_dz_emit(Dz a) {
     }
     if (err) return;
     const bool win = dz_wins(a, n, e);
-    const unsigned long long bal = __ballot(win);
-    if (lane == 0) s_w[wv] = __popcll(bal);
-    __syncthreads();
-    int rank = a.bsum[blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wv; w++) rank += s_w[w];
+    int total;
+    const int rank = a.bsum[blockIdx.x] + block_rank(win, s_w, total);
     if (!win || rank >= a.cap) return;
     const double* p = dz_entry(a, n, e);
     a.out[3 * (size_t)rank] = p[0];
@@ -558,13 +503,6 @@ __global__ __launch_bounds__(kBlk) void k_dz_emit(Dz a) {
 
 __global__ void k_dz_empty(int* counts) {
     if (threadIdx.x < 4) counts[threadIdx.x] = 0;
-}
-
-template <class T>
-T* carve(char*& p, size_t count) {
-    T* r = reinterpret_cast<T*>(p);
-    p += up256(count * sizeof(T));
-    return r;
 }
 
 int log2_ceil(size_t v) {
@@ -592,6 +530,7 @@ int cloud_normals(vs_ctx* ctx, const double* d_pts, int n_max, int k, double* d_
     return VS_OK;
 }
 
+// n_max <= VS_CLOUD_MAX_POINTS is the entry points' check (cloud_size_check, before they size their staging by it).
 int cloud_densify(vs_ctx* ctx, const double* d_pts, int n_max, const vs_cloud_densify_config& c,
                   int cap, double* d_out, int* d_src, int* d_counts, hipStream_t s) {
     const double r = c.search_radius, step = c.fill_step;
@@ -609,8 +548,8 @@ int cloud_densify(vs_ctx* ctx, const double* d_pts, int n_max, const vs_cloud_de
         return VS_ERR_CAPACITY;
     }
     const int Gs = (int)per_axis, G = Gs * Gs;
-    if (n_max > VS_CLOUD_MAX_POINTS || (long long)n_max * (1 + G) > kMaxEntries) {
-        set_error("vs_cloud_densify: more than VS_CLOUD_MAX_POINTS points or 2^24 points and lattice nodes");
+    if ((long long)n_max * (1 + G) > kMaxEntries) {
+        set_error("vs_cloud_densify: more than 2^24 points and lattice nodes");
         return VS_ERR_CAPACITY;
     }
     if (n_max == 0) {
@@ -640,25 +579,26 @@ int cloud_densify(vs_ctx* ctx, const double* d_pts, int n_max, const vs_cloud_de
     a.cap = cap, a.out = d_out, a.src = d_src, a.counts = d_counts;
 
     const size_t slots = (size_t)a.slot_mask + 1, nG = (size_t)n_max * G;
-    const size_t bytes = up256((size_t)n_max * 24) * 2 + up256((size_t)n_max * 8) * 2 + up256((size_t)n_max * 4) +
-                         up256((size_t)(a.T + 1) * 4) * 2 + up256(kStWords * 4) + up256(nG * 24) + up256(nG) +
-                         up256(slots * 8) + up256(slots * 4) + up256((size_t)a.E * 4) + up256((size_t)(a.nblk + 1) * 4);
-    VS_CHECK(ctx->densify.ensure(bytes));
-    char* p = ctx->densify.as<char>();
-    a.normals = carve<double>(p, (size_t)n_max * 3);
-    a.spts = carve<double>(p, (size_t)n_max * 3);
-    a.pkey = carve<unsigned long long>(p, n_max);
-    a.skey = carve<unsigned long long>(p, n_max);
-    a.sidx = carve<int>(p, n_max);
-    a.hist = carve<int>(p, a.T + 1);
-    a.cursor = carve<int>(p, a.T + 1);
-    a.state = carve<int>(p, kStWords);
-    a.cand = carve<double>(p, nG * 3);
-    a.cflag = carve<uint8_t>(p, nG);
-    a.tkeys = carve<unsigned long long>(p, slots);
-    a.tranks = carve<int>(p, slots);
-    a.eslot = carve<int>(p, a.E);
-    a.bsum = carve<int>(p, a.nblk + 1);
+    if ((size_t)a.T + 1 > slots) {  // k_dz_init's loop; cannot fire for an n and G that densify_check admits
+        set_error("vs_cloud_densify: the voxel table is shorter than the cell grid's histogram");
+        return VS_ERR_CAPACITY;
+    }
+    VS_CHECK(carve_buf(ctx->densify, [&](Carver& p) {
+        a.normals = p.take<double>((size_t)n_max * 3);
+        a.spts = p.take<double>((size_t)n_max * 3);
+        a.pkey = p.take<unsigned long long>(n_max);
+        a.skey = p.take<unsigned long long>(n_max);
+        a.sidx = p.take<int>(n_max);
+        a.hist = p.take<int>(a.T + 1);
+        a.cursor = p.take<int>(a.T);
+        a.state = p.take<int>(kStWords);
+        a.cand = p.take<double>(nG * 3);
+        a.cflag = p.take<uint8_t>(nG);
+        a.tkeys = p.take<unsigned long long>(slots);
+        a.tranks = p.take<int>(slots);
+        a.eslot = p.take<int>(a.E);
+        a.bsum = p.take<int>(a.nblk + 1);
+    }));
 
     const int pblocks = (n_max + 255) / 256;
     const bool work = n_max >= kMinPoints;  // below: the input unchanged
@@ -701,30 +641,29 @@ void vs_cloud_densify_default_config(vs_cloud_densify_config* c) {
 int vs_cloud_normals_dev(vs_ctx* ctx, const double* d_pts, int n, int k, double* d_normals, double* d_eig,
                          void* stream) {
     VS_ARG(ctx && d_normals && n >= 0 && (n == 0 || d_pts) && k >= 1, "vs_cloud_normals_dev: null argument or bad size");
-    if (n > VS_CLOUD_MAX_POINTS || k > VS_CLOUD_MAX_K) {
-        set_error("vs_cloud_normals_dev: more than VS_CLOUD_MAX_POINTS points or VS_CLOUD_MAX_K neighbours");
-        return VS_ERR_CAPACITY;
-    }
+    VS_CHECK(cloud_size_check("vs_cloud_normals_dev", n, k));
     VS_HIP(hipSetDevice(ctx->device));
     return cloud_normals(ctx, d_pts, n, k, d_normals, d_eig, stream ? (hipStream_t)stream : ctx->stream);
 }
 
 int vs_cloud_normals(vs_ctx* ctx, const double* pts, int n, int k, double* normals, double* eig) {
     VS_ARG(ctx && normals && n >= 0 && (n == 0 || pts), "vs_cloud_normals: null argument");
-    if (n > VS_CLOUD_MAX_POINTS) {
-        set_error("vs_cloud_normals: more than VS_CLOUD_MAX_POINTS points");
-        return VS_ERR_CAPACITY;
-    }
     if (n == 0) return VS_OK;
+    VS_CHECK(cloud_size_check("vs_cloud_normals", n, k));  // before the staging is sized by n
+    VS_ARG(k >= 1, "vs_cloud_normals: bad size");
     VS_HIP(hipSetDevice(ctx->device));
     const hipStream_t s = ctx->stream;
     const size_t pb = (size_t)n * 3 * sizeof(double);
-    VS_CHECK(ctx->h_aux0.ensure(3 * pb));
-    double* d_in = ctx->h_aux0.as<double>();
+    double *d_in, *d_nrm, *d_eig;
+    VS_CHECK(carve_buf(ctx->h_aux0, [&](Carver& h) {
+        d_in = h.take<double>((size_t)n * 3);
+        d_nrm = h.take<double>((size_t)n * 3);
+        d_eig = h.take<double>((size_t)n * 3);
+    }));
     VS_HIP(hipMemcpyAsync(d_in, pts, pb, hipMemcpyHostToDevice, s));
-    VS_CHECK(vs_cloud_normals_dev(ctx, d_in, n, k, d_in + 3 * (size_t)n, d_in + 6 * (size_t)n, s));
-    VS_HIP(hipMemcpyAsync(normals, d_in + 3 * (size_t)n, pb, hipMemcpyDeviceToHost, s));
-    if (eig) VS_HIP(hipMemcpyAsync(eig, d_in + 6 * (size_t)n, pb, hipMemcpyDeviceToHost, s));
+    VS_CHECK(cloud_normals(ctx, d_in, n, k, d_nrm, d_eig, s));
+    VS_HIP(hipMemcpyAsync(normals, d_nrm, pb, hipMemcpyDeviceToHost, s));
+    if (eig) VS_HIP(hipMemcpyAsync(eig, d_eig, pb, hipMemcpyDeviceToHost, s));
     VS_HIP(hipStreamSynchronize(s));
     return VS_OK;
 }
@@ -733,35 +672,29 @@ int vs_cloud_densify_dev(vs_ctx* ctx, const double* d_pts, int n, const vs_cloud
                          double* d_out, int* d_src, int* d_counts, void* stream) {
     VS_ARG(ctx && d_out && d_src && d_counts && n >= 0 && cap >= 0 && (n == 0 || d_pts),
            "vs_cloud_densify_dev: null argument or bad size");
-    vs_cloud_densify_config c;
-    if (cfg)
-        c = *cfg;
-    else
-        vs_cloud_densify_default_config(&c);
+    VS_CHECK(cloud_size_check("vs_cloud_densify", n, 0));
     VS_HIP(hipSetDevice(ctx->device));
-    return cloud_densify(ctx, d_pts, n, c, cap, d_out, d_src, d_counts,
+    return cloud_densify(ctx, d_pts, n, config_or(cfg, vs_cloud_densify_default_config), cap, d_out, d_src, d_counts,
                          stream ? (hipStream_t)stream : ctx->stream);
 }
 
 int vs_cloud_densify(vs_ctx* ctx, const double* pts, int n, const vs_cloud_densify_config* cfg, int cap, double* out,
                      int* src, int counts[4]) {
     VS_ARG(ctx && out && src && counts && n >= 0 && cap >= 0 && (n == 0 || pts), "vs_cloud_densify: null argument");
-    if (n > VS_CLOUD_MAX_POINTS) {
-        set_error("vs_cloud_densify: more than VS_CLOUD_MAX_POINTS points");
-        return VS_ERR_CAPACITY;
-    }
+    VS_CHECK(cloud_size_check("vs_cloud_densify", n, 0));
     VS_HIP(hipSetDevice(ctx->device));
     const hipStream_t s = ctx->stream;
-    const size_t ib = up256((size_t)std::max(n, 1) * 3 * sizeof(double));
-    const size_t ob = up256((size_t)std::max(cap, 1) * 3 * sizeof(double)), sb = up256((size_t)std::max(cap, 1) * sizeof(int));
-    VS_CHECK(ctx->h_aux0.ensure(ib + ob + sb + 4 * sizeof(int)));
-    char* base = ctx->h_aux0.as<char>();
-    double* d_in = reinterpret_cast<double*>(base);
-    double* d_out = reinterpret_cast<double*>(base + ib);
-    int* d_src = reinterpret_cast<int*>(base + ib + ob);
-    int* d_counts = reinterpret_cast<int*>(base + ib + ob + sb);
+    double *d_in, *d_out;
+    int *d_src, *d_counts;
+    VS_CHECK(carve_buf(ctx->h_aux0, [&](Carver& h) {
+        d_in = h.take<double>((size_t)std::max(n, 1) * 3);
+        d_out = h.take<double>((size_t)std::max(cap, 1) * 3);
+        d_src = h.take<int>(std::max(cap, 1));
+        d_counts = h.take<int>(4);
+    }));
     if (n > 0) VS_HIP(hipMemcpyAsync(d_in, pts, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    VS_CHECK(vs_cloud_densify_dev(ctx, d_in, n, cfg, cap, d_out, d_src, d_counts, s));
+    VS_CHECK(cloud_densify(ctx, d_in, n, config_or(cfg, vs_cloud_densify_default_config), cap, d_out, d_src, d_counts,
+                           s));
     VS_HIP(hipMemcpyAsync(counts, d_counts, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
     VS_HIP(hipStreamSynchronize(s));
     if (counts[2] < 0) {

@@ -318,23 +318,6 @@ int emat_points(vs_ctx* ctx, int P, const float* d_p1, const float* d_p2, const 
 // 0 drops the point before the box clip (a tracker's validity flags); d_idx indexes the input.
 int cloud_filter(vs_ctx* ctx, const double* d_pts, int n, const uint8_t* d_pre, const vs_cloud_filter_config& c,
                  double* d_out, int* d_idx, int* d_counts, hipStream_t s);
-// cloud.hip's search, shared with densify.hip: the context's scratch for clouds of up to n points, k neighbours
-// and S partial lists; k_cloud_knn writes part_d2 / part_idx [S][k][n_max], each list ascending by (d2, index).
-constexpr int kKnnLanes = 256;    // queries per workgroup
-constexpr int kKnnMaxSplit = 64;  // workgroups per query block
-constexpr int kNoIdx = 0x7fffffff;  // an empty list slot (d2 = +inf)
-// a count that exists only on the device (launches are sized for the host's upper bound n_max)
-__device__ __forceinline__ int dev_count(const int* d_n, int n_max) { return d_n ? min(*d_n, n_max) : n_max; }
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-struct CloudScratch {
-    double *part_d2, *mean, *pts_a, *pts_b;
-    int *part_idx, *idx_a, *idx_b;
-    uint8_t* flags;
-};
-int knn_split(vs_ctx* ctx, int n, int forced);
-int cloud_scratch(vs_ctx* ctx, int n, int k, int S, CloudScratch* cs);
-void launch_knn(const CloudScratch& cs, const double* d_pts, const int* d_n, int n_max, int k, int S, int skip_small,
-                hipStream_t s);
 // Surface densification and normals (densify.hip; vs_cloud_densify_dev, vs_cloud_normals_dev).
 int cloud_normals(vs_ctx* ctx, const double* d_pts, int n_max, int k, double* d_normals, double* d_eig, hipStream_t s);
 int cloud_densify(vs_ctx* ctx, const double* d_pts, int n_max, const vs_cloud_densify_config& c,
