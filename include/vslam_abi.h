@@ -533,6 +533,33 @@ int vs_cloud_filter(vs_ctx* ctx, const double* pts, int n, const vs_cloud_filter
  * to pts (x 3) and idx (indices into vs_slam_map's list), each nullable.  Synchronous. */
 int vs_slam_filtered_map(vs_slam* slam, int valid_only, int cap, double* pts, int* idx, int* n);
 
+/* ---- the same searches on a uniform cell grid (csrc/cloud_grid.hip) ----
+ * An exact k-NN that returns the lists of vs_cloud_knn_dev bit for bit (the same d2 expression, the
+ * same (d2, index) order) in time that grows with n, for clouds of up to VS_CLOUD_GRID_MAX_POINTS
+ * points.  The normals and the filter below differ from their brute-force namesakes only in the
+ * search and in that limit.  The filter shares it: k_cloud_compact and k_cloud_threshold index with
+ * size_t and carry nothing tied to 2^18 (a compaction block counts the flag bytes before it, so the
+ * three compactions read n^2 / 32 bytes in all, and the threshold is one workgroup striding over n:
+ * both stay below the searches' time, neither sets a lower limit).
+ * cell_edge: the grid's edge; 0 = chosen on the device from a sample of the cloud.  Either is raised
+ * on the device to max|coordinate| / 2^19, so any finite cloud packs into 21 bits per axis.
+ * max_rings: rings of cells searched around a query before it is handed to the coarser grids and
+ * last to a pass over all points; 0 = the default (4).  Results depend on neither, only the time.
+ * d_stats (nullable) [2] = {queries finished on a grid, queries finished by the pass over all
+ * points}.  The scratch lives in the context: one call per context at a time. */
+#define VS_CLOUD_GRID_MAX_POINTS (1 << 23)
+/* d_nbr / d_d2 [n][k] as vs_cloud_knn_dev writes them.  cell_edge < 0, max_rings < 0, k < 1:
+ * VS_ERR_ARG; k > VS_CLOUD_MAX_K or n > VS_CLOUD_GRID_MAX_POINTS: VS_ERR_CAPACITY (before anything
+ * is allocated or read); n == 0: nothing happens.  Enqueue only. */
+int vs_cloud_knn_grid_dev(vs_ctx* ctx, const double* d_pts, int n, int k, double cell_edge, int max_rings, int* d_nbr,
+                          double* d_d2, int* d_stats, void* stream);
+/* vs_cloud_filter_dev / vs_cloud_filter with both stages' searches on the grid (rebuilt for the
+ * second stage on the first's survivors, whose count stays on the device). */
+int vs_cloud_filter_grid_dev(vs_ctx* ctx, const double* d_pts, int n, const vs_cloud_filter_config* cfg, double* d_out,
+                             int* d_idx, int* d_counts, void* stream);
+int vs_cloud_filter_grid(vs_ctx* ctx, const double* pts, int n, const vs_cloud_filter_config* cfg, double* out,
+                         int* idx, int counts[3]);
+
 /* ---- surface densification and normals (main.cpp:846-965 after the filter, :645-672, :1369-1387) ----
  * estimate_normals: point i's list is i itself, then its min(k, n) - 1 nearest others by (d2, index);
  * with fewer than 3 entries the normal is (0, 0, 1) (eigenvalues 0), otherwise the eigenvector of the
@@ -562,6 +589,10 @@ void vs_cloud_densify_default_config(vs_cloud_densify_config* cfg);
 int vs_cloud_normals_dev(vs_ctx* ctx, const double* d_pts, int n, int k, double* d_normals, double* d_eig, void* stream);
 /* The same on host buffers; synchronous. */
 int vs_cloud_normals(vs_ctx* ctx, const double* pts, int n, int k, double* normals, double* eig);
+/* The same with the search on the cell grid (n <= VS_CLOUD_GRID_MAX_POINTS). */
+int vs_cloud_normals_grid_dev(vs_ctx* ctx, const double* d_pts, int n, int k, double* d_normals, double* d_eig,
+                              void* stream);
+int vs_cloud_normals_grid(vs_ctx* ctx, const double* pts, int n, int k, double* normals, double* eig);
 /* d_out [cap][3], d_src [cap]: an input point that survives carries its input index, a filled point
  * -(i + 1) with i the input point whose plane produced it.  d_counts [4] = {input points that
  * survive, filled points that survive, their total, points skipped at the neighbour cap}; when the

@@ -6,6 +6,11 @@ at the tracking tests' map sizes, with device events over repeated calls after w
 
 --densify times vs_cloud_normals_dev (k = 20) and vs_cloud_densify_dev with the same protocol on the same cloud with
 holes cut into the planes, and a second pass with the context's stage profile on gives each kernel's share.
+    python tools/bench_cloud.py --grid [--out profiles/cloud_knn_grid.json]
+
+--grid times the cell-grid entry points (vs_cloud_knn_grid_dev, vs_cloud_normals_grid_dev with k = 20,
+vs_cloud_filter_grid_dev) beside their brute-force counterparts in the same run, then alone at 2^20 points, and
+reports the stats pair and each kernel's share and time per launch from a profile pass of its own.
 
 Pair tests per filter call = n0^2 + n1^2 (n0 points enter statistical_outlier_removal, n1 enter
 surface_aware_filter: every query meets every candidate).  One pair test is 3 sub, 3 mul, 2 add and
@@ -75,6 +80,51 @@ def densify_runs(ctx, sizes, stream, dev):
     return runs
 
 
+def grid_runs(ctx, args, cfg, stream, dev):
+    s, runs = stream.cuda_stream, []
+    for n in args.sizes + [1 << 20]:
+        brute = n <= (1 << 18)
+        p = torch.from_numpy(cloud(n)).to(dev)
+        out = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        idx = torch.zeros(n, dtype=torch.int32, device=dev)
+        cnt = torch.zeros(3, dtype=torch.int32, device=dev)
+        nbr = torch.zeros((n, args.k), dtype=torch.int32, device=dev)
+        d2 = torch.zeros((n, args.k), dtype=torch.float64, device=dev)
+        stats = torch.zeros(2, dtype=torch.int32, device=dev)
+        calls = {
+            "knn": lambda g: (ctx.cloud_knn_grid_dev(p.data_ptr(), n, args.k, nbr.data_ptr(), d2.data_ptr(), 0.0, 0,
+                                                     stats.data_ptr(), s) if g else
+                              ctx.cloud_knn_dev(p.data_ptr(), n, args.k, nbr.data_ptr(), d2.data_ptr(), 0, s)),
+            "normals": lambda g: ctx.cloud_normals_dev(p.data_ptr(), n, 20, out.data_ptr(), None, s, grid=g),
+            "filter": lambda g: ctx.cloud_filter_dev(p.data_ptr(), n, cfg, out.data_ptr(), idx.data_ptr(),
+                                                     cnt.data_ptr(), s, grid=g),
+        }
+        run = {"n": n, "reps_per_round": {}}
+        for name, call in calls.items():
+            for g in ([False, True] if brute else [True]):
+                reps = max(3, min(100, int((2e7 if g else 2e10 / n) / n)))
+                ms = timed(lambda: call(g), stream, 5, reps)
+                key = name + ("_grid" if g else "")
+                run[key + "_ms_rounds"], run[key + "_ms"] = ms, float(np.median(ms))
+                run["reps_per_round"][key] = reps
+            if brute:
+                run[name + "_brute_over_grid"] = run[name + "_ms"] / run[name + "_grid_ms"]
+        run["stats"] = stats.cpu().numpy().tolist()
+        run["filter_counts"] = cnt.cpu().numpy().tolist()
+        ctx.profile(True)  # a pass of its own: the stage events are not part of the timed calls above
+        ctx.profile_reset()
+        for _ in range(5):
+            calls["knn"](True)
+        torch.cuda.synchronize()
+        prof = ctx.profile_read()
+        ctx.profile(False)
+        tot = sum(ms for ms, _ in prof.values()) or 1.0
+        run["knn_grid_kernel_share"] = {k: ms / tot for k, (ms, _) in prof.items()}
+        run["knn_grid_kernel_ms_per_launch"] = {k: ms / max(c, 1) for k, (ms, c) in prof.items()}
+        runs.append(run)
+    return runs
+
+
 def timed(fn, stream, warm, reps, rounds=5):
     """ms per call: events on the stream the calls are enqueued on, around reps calls, per round."""
     for _ in range(warm):
@@ -98,6 +148,7 @@ def main():
     ap.add_argument("--sizes", type=int, nargs="+", default=[12000, 60000])
     ap.add_argument("--k", type=int, default=25)
     ap.add_argument("--densify", action="store_true")
+    ap.add_argument("--grid", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     cus = torch.cuda.get_device_properties(0).multi_processor_count
@@ -107,6 +158,8 @@ def main():
         stream = torch.cuda.ExternalStream(ctx.stream)  # the context's own stream
         if args.densify:
             res = {"device": res["device"], "cus": cus, "runs": densify_runs(ctx, args.sizes, stream, dev)}
+        elif args.grid:
+            res["runs"] = grid_runs(ctx, args, cfg, stream, dev)
         else:
             res["runs"] = filter_runs(ctx, args, cfg, cus, stream, dev)
     line = json.dumps(res)

@@ -339,10 +339,11 @@ int cloud_scratch(vs_ctx* ctx, int n, int k, int S, CloudScratch* cs) {
     });
 }
 
-int cloud_size_check(const char* who, int n, int k) {
-    if (n <= VS_CLOUD_MAX_POINTS && k <= VS_CLOUD_MAX_K) return VS_OK;
-    set_error(std::string(who) + (n > VS_CLOUD_MAX_POINTS ? ": more than VS_CLOUD_MAX_POINTS points"
-                                                          : ": more than VS_CLOUD_MAX_K neighbours"));
+int cloud_size_check(const char* who, int n, int k, int max_points) {
+    if (n <= max_points && k <= VS_CLOUD_MAX_K) return VS_OK;
+    set_error(std::string(who) + (n <= max_points                   ? ": more than VS_CLOUD_MAX_K neighbours"
+                                  : max_points == VS_CLOUD_MAX_POINTS ? ": more than VS_CLOUD_MAX_POINTS points"
+                                                                      : ": more than VS_CLOUD_GRID_MAX_POINTS points"));
     return VS_ERR_CAPACITY;
 }
 
@@ -350,6 +351,14 @@ void launch_knn(const CloudScratch& cs, const double* d_pts, const int* d_n, int
                 hipStream_t s) {
     hipLaunchKernelGGL(k_cloud_knn, dim3((n_max + kKnnLanes - 1) / kKnnLanes, S), dim3(kKnnLanes), 0, s, d_pts, d_n,
                        n_max, k, skip_small, cs.part_d2, cs.part_idx);
+}
+
+// the single list [k][n] of a grid search as vs_cloud_knn_dev's [n][k] output (k_cloud_reduce's list mode)
+int cloud_knn_lists(const CloudScratch& cs, const double* d_pts, int n, int k, int* d_nbr, double* d_d2, hipStream_t s) {
+    ReduceArgs r{d_pts, nullptr, n, k, 1, kReduceKnn, cs.part_d2, cs.part_idx, 0.0, nullptr, nullptr, d_nbr, d_d2};
+    hipLaunchKernelGGL(k_cloud_reduce, dim3((n + kKnnLanes - 1) / kKnnLanes), dim3(kKnnLanes), 0, s, r);
+    VS_HIP(hipGetLastError());
+    return VS_OK;
 }
 
 namespace {
@@ -360,18 +369,25 @@ void launch_compact(const double* in, const int* idx_in, const uint8_t* flags, c
                        idx_in, flags, d_n_in, n_max, out, idx_out, d_n_out);
 }
 
-int filter_check(const vs_cloud_filter_config& c, int n) {
+int filter_check(const vs_cloud_filter_config& c, int n, bool grid) {
     VS_ARG(c.sor_k >= 0 && c.surf_k >= 0, "vs_cloud_filter: negative neighbour count");
-    return cloud_size_check("vs_cloud_filter", n, std::max(c.sor_k, c.surf_k));
+    return cloud_size_check("vs_cloud_filter", n, std::max(c.sor_k, c.surf_k),
+                            grid ? VS_CLOUD_GRID_MAX_POINTS : VS_CLOUD_MAX_POINTS);
 }
 
 // the launches of cloud_filter; the caller has run filter_check
 int filter_enqueue(vs_ctx* ctx, const double* d_pts, int n, const uint8_t* d_pre, const vs_cloud_filter_config& c,
-                   double* d_out, int* d_idx, int* d_counts, hipStream_t s) {
-    const int S = n > 0 ? knn_split(ctx, n, 0) : 1;
+                   double* d_out, int* d_idx, int* d_counts, hipStream_t s, bool grid) {
+    const int S = n > 0 && !grid ? knn_split(ctx, n, 0) : 1;
     CloudScratch cs;
     VS_CHECK(cloud_scratch(ctx, std::max(n, 1), std::max(c.sor_k, c.surf_k), S, &cs));
-    ProfScope ps(ctx, "cloud_filter", s);
+    ProfScope ps(ctx, grid ? "cloud_filter_grid" : "cloud_filter", s);
+    // a stage's search: brute force, or the cell grid rebuilt on the stage's points (cloud_grid.hip)
+    auto search = [&](const double* pts, const int* d_n, int k) {
+        if (grid) return launch_knn_grid(ctx, cs, pts, d_n, n, k, 1, 0.0, 0, nullptr, s);
+        launch_knn(cs, pts, d_n, n, k, S, 1, s);
+        return (int)VS_OK;
+    };
     const int qblocks = std::max(1, (n + kKnnLanes - 1) / kKnnLanes);
     // the clip (main.cpp:1193-1209)
     const bool clip = c.use_bbox || d_pre;
@@ -383,7 +399,7 @@ int filter_enqueue(vs_ctx* ctx, const double* d_pts, int n, const uint8_t* d_pre
     launch_compact(d_pts, nullptr, clip ? cs.flags : nullptr, nullptr, n, cs.pts_a, cs.idx_a, d_counts, s);
     // stage A (main.cpp:512-563) on the clipped points
     if (c.sor_k > 0 && n > 0) {
-        launch_knn(cs, cs.pts_a, d_counts, n, c.sor_k, S, 1, s);
+        VS_CHECK(search(cs.pts_a, d_counts, c.sor_k));
         ReduceArgs r{cs.pts_a, d_counts, n, c.sor_k, S, kReduceMean, cs.part_d2, cs.part_idx, 0.0, cs.mean, nullptr,
                      nullptr, nullptr};
         hipLaunchKernelGGL(k_cloud_reduce, dim3(qblocks), dim3(kKnnLanes), 0, s, r);
@@ -394,7 +410,7 @@ int filter_enqueue(vs_ctx* ctx, const double* d_pts, int n, const uint8_t* d_pre
                    s);
     // stage B (main.cpp:568-642) on stage A's survivors
     if (c.surf_k > 0 && n > 0) {
-        launch_knn(cs, cs.pts_b, d_counts + 1, n, c.surf_k, S, 1, s);
+        VS_CHECK(search(cs.pts_b, d_counts + 1, c.surf_k));
         ReduceArgs r{cs.pts_b, d_counts + 1, n, c.surf_k, S, kReduceSurface, cs.part_d2, cs.part_idx,
                      c.surf_min_anisotropy, nullptr, cs.flags, nullptr, nullptr};
         hipLaunchKernelGGL(k_cloud_reduce, dim3(qblocks), dim3(kKnnLanes), 0, s, r);
@@ -408,9 +424,38 @@ int filter_enqueue(vs_ctx* ctx, const double* d_pts, int n, const uint8_t* d_pre
 }  // namespace
 
 int cloud_filter(vs_ctx* ctx, const double* d_pts, int n, const uint8_t* d_pre, const vs_cloud_filter_config& c,
-                 double* d_out, int* d_idx, int* d_counts, hipStream_t s) {
-    VS_CHECK(filter_check(c, n));
-    return filter_enqueue(ctx, d_pts, n, d_pre, c, d_out, d_idx, d_counts, s);
+                 double* d_out, int* d_idx, int* d_counts, hipStream_t s, bool grid) {
+    VS_CHECK(filter_check(c, n, grid));
+    return filter_enqueue(ctx, d_pts, n, d_pre, c, d_out, d_idx, d_counts, s, grid);
+}
+
+int cloud_filter_host(vs_ctx* ctx, const double* pts, int n, const vs_cloud_filter_config* cfg, double* out, int* idx,
+                      int counts[3], bool grid) {
+    VS_ARG(ctx && out && idx && counts && n >= 0 && (n == 0 || pts), "vs_cloud_filter: null argument");
+    const vs_cloud_filter_config c = config_or(cfg, vs_cloud_filter_default_config);
+    VS_CHECK(filter_check(c, n, grid));  // before the staging is sized by n
+    VS_HIP(hipSetDevice(ctx->device));
+    const hipStream_t s = ctx->stream;
+    const size_t cnt = (size_t)std::max(n, 1);
+    double *d_in, *d_out;
+    int *d_idx, *d_counts;
+    VS_CHECK(carve_buf(ctx->h_aux0, [&](Carver& h) {
+        d_in = h.take<double>(cnt * 3);
+        d_out = h.take<double>(cnt * 3);
+        d_idx = h.take<int>(cnt);
+        d_counts = h.take<int>(3);
+    }));
+    if (n > 0) VS_HIP(hipMemcpyAsync(d_in, pts, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+    VS_CHECK(filter_enqueue(ctx, d_in, n, nullptr, c, d_out, d_idx, d_counts, s, grid));
+    VS_HIP(hipMemcpyAsync(counts, d_counts, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+    VS_HIP(hipStreamSynchronize(s));
+    const int m = counts[2];
+    if (m > 0) {
+        VS_HIP(hipMemcpyAsync(out, d_out, (size_t)m * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+        VS_HIP(hipMemcpyAsync(idx, d_idx, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s));
+        VS_HIP(hipStreamSynchronize(s));
+    }
+    return VS_OK;
 }
 
 }  // namespace vs
@@ -457,31 +502,7 @@ int vs_cloud_filter_dev(vs_ctx* ctx, const double* d_pts, int n, const vs_cloud_
 
 int vs_cloud_filter(vs_ctx* ctx, const double* pts, int n, const vs_cloud_filter_config* cfg, double* out, int* idx,
                     int counts[3]) {
-    VS_ARG(ctx && out && idx && counts && n >= 0 && (n == 0 || pts), "vs_cloud_filter: null argument");
-    const vs_cloud_filter_config c = config_or(cfg, vs_cloud_filter_default_config);
-    VS_CHECK(filter_check(c, n));  // before the staging is sized by n
-    VS_HIP(hipSetDevice(ctx->device));
-    const hipStream_t s = ctx->stream;
-    const size_t cnt = (size_t)std::max(n, 1);
-    double *d_in, *d_out;
-    int *d_idx, *d_counts;
-    VS_CHECK(carve_buf(ctx->h_aux0, [&](Carver& h) {
-        d_in = h.take<double>(cnt * 3);
-        d_out = h.take<double>(cnt * 3);
-        d_idx = h.take<int>(cnt);
-        d_counts = h.take<int>(3);
-    }));
-    if (n > 0) VS_HIP(hipMemcpyAsync(d_in, pts, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    VS_CHECK(filter_enqueue(ctx, d_in, n, nullptr, c, d_out, d_idx, d_counts, s));
-    VS_HIP(hipMemcpyAsync(counts, d_counts, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
-    VS_HIP(hipStreamSynchronize(s));
-    const int m = counts[2];
-    if (m > 0) {
-        VS_HIP(hipMemcpyAsync(out, d_out, (size_t)m * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-        VS_HIP(hipMemcpyAsync(idx, d_idx, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s));
-        VS_HIP(hipStreamSynchronize(s));
-    }
-    return VS_OK;
+    return cloud_filter_host(ctx, pts, n, cfg, out, idx, counts, false);
 }
 
 }  // extern "C"

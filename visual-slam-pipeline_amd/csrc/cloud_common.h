@@ -11,6 +11,7 @@ namespace vs {
 constexpr int kKnnLanes = 256;    // queries per workgroup
 constexpr int kKnnMaxSplit = 64;  // workgroups per query block
 constexpr int kNoIdx = 0x7fffffff;  // an empty list slot (d2 = +inf)
+constexpr int kAxisBits = 21, kAxisBias = 1 << 20;  // a packed cell or voxel coordinate: 21 bits per axis
 // a count that exists only on the device (launches are sized for the host's upper bound n_max)
 __device__ __forceinline__ int dev_count(const int* d_n, int n_max) { return d_n ? min(*d_n, n_max) : n_max; }
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -26,8 +27,18 @@ int knn_split(vs_ctx* ctx, int n, int forced);
 int cloud_scratch(vs_ctx* ctx, int n, int k, int S, CloudScratch* cs);
 void launch_knn(const CloudScratch& cs, const double* d_pts, const int* d_n, int n_max, int k, int S, int skip_small,
                 hipStream_t s);
+// cloud_grid.hip's search on a cell grid: the same lists as launch_knn with S = 1, written to cs.part_d2 / part_idx
+// [k][n_max].  cell_edge 0: derived on the device; max_rings 0: the default; d_stats (nullable) [2] = queries finished
+// by the rings, by the full scan.  The grid's own scratch is the context's (cloud_grid), sized here.
+int launch_knn_grid(vs_ctx* ctx, const CloudScratch& cs, const double* d_pts, const int* d_n, int n_max, int k,
+                    int skip_small, double cell_edge, int max_rings, int* d_stats, hipStream_t s);
+int cloud_knn_lists(const CloudScratch& cs, const double* d_pts, int n, int k, int* d_nbr, double* d_d2, hipStream_t s);
 // VS_ERR_CAPACITY (and the message) when n or k is above what the search holds; called once per entry path
-int cloud_size_check(const char* who, int n, int k);
+int cloud_size_check(const char* who, int n, int k, int max_points = VS_CLOUD_MAX_POINTS);
+// the host-buffer calls behind vs_cloud_filter / vs_cloud_filter_grid and vs_cloud_normals / vs_cloud_normals_grid
+int cloud_filter_host(vs_ctx* ctx, const double* pts, int n, const vs_cloud_filter_config* cfg, double* out, int* idx,
+                      int counts[3], bool grid);
+int cloud_normals_host(vs_ctx* ctx, const double* pts, int n, int k, double* normals, double* eig, bool grid);
 // a caller's configuration, or the defaults that def writes
 template <class C>
 C config_or(const C* cfg, void (*def)(C*)) {
@@ -61,6 +72,15 @@ __device__ __forceinline__ void knn_merge(const double* part_d2, const int* part
         cur[bs * kKnnLanes]++;
         emit(t, bd, bi);
     }
+}
+
+// Three cell or voxel coordinates (each in [0, 2^21)) in one word, and the bucket or slot of such a word.
+__device__ __forceinline__ unsigned long long pack3(long long x, long long y, long long z) {
+    return ((unsigned long long)x << (2 * kAxisBits)) | ((unsigned long long)y << kAxisBits) | (unsigned long long)z;
+}
+__device__ __forceinline__ bool fits(long long v) { return v >= 0 && v < (1ll << kAxisBits); }
+__device__ __forceinline__ unsigned hash_bits(unsigned long long key, int shift) {
+    return (unsigned)((key * 0x9E3779B97F4A7C15ull) >> shift);
 }
 
 // The six sums of a 3 x 3 scatter matrix, each in the order of the add calls.

@@ -51,7 +51,6 @@ namespace {
 constexpr int kCap = VS_DENSIFY_MAX_NEIGHBOURS;
 constexpr int kBlk = 1024;                   // entries per compaction block
 constexpr long long kMaxEntries = 1ll << 24; // n (1 + lattice nodes)
-constexpr int kAxisBits = 21, kAxisBias = 1 << 20;
 constexpr unsigned long long kEmpty = ~0ull;
 constexpr int kNormalK = 20;  // main.cpp:861
 constexpr int kMinPoints = 20;  // main.cpp:850
@@ -63,14 +62,6 @@ __device__ __forceinline__ void orient(double& x, double& y, double& z) {
     const double ax = fabs(x), ay = fabs(y), az = fabs(z);
     const double lead = (ax >= ay && ax >= az) ? x : (ay >= az ? y : z);
     if (lead < 0) x = -x, y = -y, z = -z;
-}
-
-__device__ __forceinline__ unsigned long long pack3(long long x, long long y, long long z) {
-    return ((unsigned long long)x << (2 * kAxisBits)) | ((unsigned long long)y << kAxisBits) | (unsigned long long)z;
-}
-__device__ __forceinline__ bool fits(long long v) { return v >= 0 && v < (1ll << kAxisBits); }
-__device__ __forceinline__ unsigned hash_bits(unsigned long long key, int shift) {
-    return (unsigned)((key * 0x9E3779B97F4A7C15ull) >> shift);
 }
 
 struct NormalArgs {
@@ -514,12 +505,14 @@ int log2_ceil(size_t v) {
 }  // namespace
 
 int cloud_normals(vs_ctx* ctx, const double* d_pts, int n_max, int k, double* d_normals, double* d_eig,
-                  hipStream_t s) {
+                  hipStream_t s, bool grid) {
     if (n_max == 0) return VS_OK;
-    const int S = knn_split(ctx, n_max, 0);
+    const int S = grid ? 1 : knn_split(ctx, n_max, 0);
     CloudScratch cs;
     VS_CHECK(cloud_scratch(ctx, n_max, std::max(k - 1, 1), S, &cs));
-    if (k >= 3) {  // k < 3: every normal is (0, 0, 1)
+    if (k >= 3 && grid) {  // k < 3: every normal is (0, 0, 1)
+        VS_CHECK(launch_knn_grid(ctx, cs, d_pts, nullptr, n_max, k - 1, 0, 0.0, 0, nullptr, s));
+    } else if (k >= 3) {
         ProfScope ps(ctx, "k_cloud_knn", s);
         launch_knn(cs, d_pts, nullptr, n_max, k - 1, S, 0, s);
     }
@@ -647,9 +640,16 @@ int vs_cloud_normals_dev(vs_ctx* ctx, const double* d_pts, int n, int k, double*
 }
 
 int vs_cloud_normals(vs_ctx* ctx, const double* pts, int n, int k, double* normals, double* eig) {
+    return cloud_normals_host(ctx, pts, n, k, normals, eig, false);
+}
+
+}  // extern "C"
+
+int vs::cloud_normals_host(vs_ctx* ctx, const double* pts, int n, int k, double* normals, double* eig, bool grid) {
     VS_ARG(ctx && normals && n >= 0 && (n == 0 || pts), "vs_cloud_normals: null argument");
     if (n == 0) return VS_OK;
-    VS_CHECK(cloud_size_check("vs_cloud_normals", n, k));  // before the staging is sized by n
+    // before the staging is sized by n
+    VS_CHECK(cloud_size_check("vs_cloud_normals", n, k, grid ? VS_CLOUD_GRID_MAX_POINTS : VS_CLOUD_MAX_POINTS));
     VS_ARG(k >= 1, "vs_cloud_normals: bad size");
     VS_HIP(hipSetDevice(ctx->device));
     const hipStream_t s = ctx->stream;
@@ -661,12 +661,14 @@ int vs_cloud_normals(vs_ctx* ctx, const double* pts, int n, int k, double* norma
         d_eig = h.take<double>((size_t)n * 3);
     }));
     VS_HIP(hipMemcpyAsync(d_in, pts, pb, hipMemcpyHostToDevice, s));
-    VS_CHECK(cloud_normals(ctx, d_in, n, k, d_nrm, d_eig, s));
+    VS_CHECK(cloud_normals(ctx, d_in, n, k, d_nrm, d_eig, s, grid));
     VS_HIP(hipMemcpyAsync(normals, d_nrm, pb, hipMemcpyDeviceToHost, s));
     if (eig) VS_HIP(hipMemcpyAsync(eig, d_eig, pb, hipMemcpyDeviceToHost, s));
     VS_HIP(hipStreamSynchronize(s));
     return VS_OK;
 }
+
+extern "C" {
 
 int vs_cloud_densify_dev(vs_ctx* ctx, const double* d_pts, int n, const vs_cloud_densify_config* cfg, int cap,
                          double* d_out, int* d_src, int* d_counts, void* stream) {

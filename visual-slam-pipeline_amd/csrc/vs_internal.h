@@ -139,6 +139,7 @@ struct vs_ctx {
     vs::DevBuf cloud;  // the cloud filter's partial k-NN lists, stage buffers and flags (cloud.hip), sized on first use
     int cloud_cus = 0;  // the device's CU count (k_cloud_knn's candidate split), read on first use
     vs::DevBuf densify;  // densify.hip: merged neighbour lists, normals, cell grid, candidates, voxel table
+    vs::DevBuf cloud_grid;  // cloud_grid.hip: the k-NN's cell grid (sorted points, bucket table), its lists and state
 
     bool prof_on = false;
     int prof_mode = 0;  // 1: every stage, 2: extraction stages only (vs_profile_enable)
@@ -317,9 +318,11 @@ int emat_points(vs_ctx* ctx, int P, const float* d_p1, const float* d_p2, const 
 // The sparse-map cloud filter (cloud.hip; vs_cloud_filter_dev).  d_pre (optional): one byte per point,
 // 0 drops the point before the box clip (a tracker's validity flags); d_idx indexes the input.
 int cloud_filter(vs_ctx* ctx, const double* d_pts, int n, const uint8_t* d_pre, const vs_cloud_filter_config& c,
-                 double* d_out, int* d_idx, int* d_counts, hipStream_t s);
+                 double* d_out, int* d_idx, int* d_counts, hipStream_t s, bool grid = false);
 // Surface densification and normals (densify.hip; vs_cloud_densify_dev, vs_cloud_normals_dev).
-int cloud_normals(vs_ctx* ctx, const double* d_pts, int n_max, int k, double* d_normals, double* d_eig, hipStream_t s);
+// grid: the searches run on cloud_grid.hip's cell grid (the same lists; n up to VS_CLOUD_GRID_MAX_POINTS).
+int cloud_normals(vs_ctx* ctx, const double* d_pts, int n_max, int k, double* d_normals, double* d_eig, hipStream_t s,
+                  bool grid = false);
 int cloud_densify(vs_ctx* ctx, const double* d_pts, int n_max, const vs_cloud_densify_config& c,
                   int cap, double* d_out, int* d_src, int* d_counts, hipStream_t s);
 // Local bundle adjustment over a gathered window (host arrays in/out, see vs_local_ba)

@@ -113,6 +113,11 @@ _SIG = {
     "vs_cloud_filter_dev": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
     "vs_cloud_filter": (_I, [_P, _P, _I, _P, _P, _P, _P]),
     "vs_slam_filtered_map": (_I, [_P, _I, _I, _P, _P, _P]),
+    "vs_cloud_knn_grid_dev": (_I, [_P, _P, _I, _I, ctypes.c_double, _I, _P, _P, _P, _P]),
+    "vs_cloud_filter_grid_dev": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
+    "vs_cloud_filter_grid": (_I, [_P, _P, _I, _P, _P, _P, _P]),
+    "vs_cloud_normals_grid_dev": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "vs_cloud_normals_grid": (_I, [_P, _P, _I, _I, _P, _P]),
     "vs_cloud_densify_default_config": (None, [_P]),
     "vs_cloud_normals_dev": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "vs_cloud_normals": (_I, [_P, _P, _I, _I, _P, _P]),
@@ -539,21 +544,39 @@ class Context:
         torch.cuda.synchronize()
         return nbr.cpu().numpy(), d2.cpu().numpy()
 
-    def cloud_filter_dev(self, d_pts, n, cfg, d_out, d_idx, d_counts, stream=None):
-        """Device pointers; cfg a CloudFilterConfig or None (the reference's values).  Enqueue only."""
-        _check(self.lib.vs_cloud_filter_dev(self.h, d_pts, n, None if cfg is None else ctypes.byref(cfg), d_out,
-                                            d_idx, d_counts, stream))
+    def cloud_knn_grid_dev(self, d_pts, n, k, d_nbr, d_d2, cell_edge=0.0, max_rings=0, d_stats=None, stream=None):
+        _check(self.lib.vs_cloud_knn_grid_dev(self.h, d_pts, n, k, cell_edge, max_rings, d_nbr, d_d2, d_stats, stream))
 
-    def cloud_filter(self, pts, cfg=None):
+    def cloud_knn_grid(self, pts, k, cell_edge=0.0, max_rings=0):
+        """cloud_knn on the cell grid (vs_cloud_knn_grid_dev; up to 2^23 points) -> (nbr, d2, stats [2] = queries
+        finished on a grid, queries finished by the pass over all points).  cell_edge 0: chosen on the device."""
+        import torch
+        p = torch.from_numpy(np.ascontiguousarray(pts, np.float64).reshape(-1, 3)).cuda()
+        n = p.shape[0]
+        nbr = torch.empty((n, k), dtype=torch.int32, device=p.device)
+        d2 = torch.empty((n, k), dtype=torch.float64, device=p.device)
+        stats = torch.zeros(2, dtype=torch.int32, device=p.device)
+        self.cloud_knn_grid_dev(p.data_ptr(), n, k, nbr.data_ptr(), d2.data_ptr(), cell_edge, max_rings,
+                                stats.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        return nbr.cpu().numpy(), d2.cpu().numpy(), stats.cpu().numpy()
+
+    def cloud_filter_dev(self, d_pts, n, cfg, d_out, d_idx, d_counts, stream=None, grid=False):
+        """Device pointers; cfg a CloudFilterConfig or None (the reference's values).  Enqueue only.
+        grid: the searches run on the cell grid (vs_cloud_filter_grid_dev)."""
+        fn = self.lib.vs_cloud_filter_grid_dev if grid else self.lib.vs_cloud_filter_dev
+        _check(fn(self.h, d_pts, n, None if cfg is None else ctypes.byref(cfg), d_out, d_idx, d_counts, stream))
+
+    def cloud_filter(self, pts, cfg=None, grid=False):
         """Host points [n, 3] -> (survivors [m, 3], their indices [m], counts [3] = after the box, after
-        statistical_outlier_removal, after surface_aware_filter)."""
+        statistical_outlier_removal, after surface_aware_filter).  grid: vs_cloud_filter_grid."""
         p = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
         n = p.shape[0]
         out = np.zeros((max(n, 1), 3), np.float64)
         idx = np.zeros(max(n, 1), np.int32)
         counts = np.zeros(3, np.int32)
-        _check(self.lib.vs_cloud_filter(self.h, _ptr(p), n, None if cfg is None else ctypes.byref(cfg), _ptr(out),
-                                        _ptr(idx), _ptr(counts)))
+        fn = self.lib.vs_cloud_filter_grid if grid else self.lib.vs_cloud_filter
+        _check(fn(self.h, _ptr(p), n, None if cfg is None else ctypes.byref(cfg), _ptr(out), _ptr(idx), _ptr(counts)))
         return out[:counts[2]], idx[:counts[2]], counts
 
     # ---- surface densification and normals (main.cpp:645-672, 846-965) ----
@@ -565,16 +588,18 @@ class Context:
             setattr(cfg, k, v)
         return cfg
 
-    def cloud_normals_dev(self, d_pts, n, k, d_normals, d_eig=None, stream=None):
-        _check(self.lib.vs_cloud_normals_dev(self.h, d_pts, n, k, d_normals, d_eig, stream))
+    def cloud_normals_dev(self, d_pts, n, k, d_normals, d_eig=None, stream=None, grid=False):
+        fn = self.lib.vs_cloud_normals_grid_dev if grid else self.lib.vs_cloud_normals_dev
+        _check(fn(self.h, d_pts, n, k, d_normals, d_eig, stream))
 
-    def cloud_normals(self, pts, k=20):
+    def cloud_normals(self, pts, k=20, grid=False):
         """Host points [n, 3] -> (normals [n, 3], eigenvalues [n, 3] descending); the largest component of
-        every normal is positive."""
+        every normal is positive.  grid: the search runs on the cell grid (vs_cloud_normals_grid)."""
         p = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
         n = p.shape[0]
         normals, eig = np.zeros((max(n, 1), 3)), np.zeros((max(n, 1), 3))
-        _check(self.lib.vs_cloud_normals(self.h, _ptr(p), n, k, _ptr(normals), _ptr(eig)))
+        fn = self.lib.vs_cloud_normals_grid if grid else self.lib.vs_cloud_normals
+        _check(fn(self.h, _ptr(p), n, k, _ptr(normals), _ptr(eig)))
         return normals[:n], eig[:n]
 
     def cloud_densify_dev(self, d_pts, n, cfg, cap, d_out, d_src, d_counts, stream=None):
