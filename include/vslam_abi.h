@@ -604,6 +604,44 @@ int vs_cloud_densify_dev(vs_ctx* ctx, const double* d_pts, int n, const vs_cloud
 int vs_cloud_densify(vs_ctx* ctx, const double* pts, int n, const vs_cloud_densify_config* cfg, int cap, double* out,
                      int* src, int counts[4]);
 
+/* ---- the fan triangulation of the cloud (main.cpp:689-774 compute_mesh; csrc/cloud_mesh.hip) ----
+ * compute_mesh restated literally, in fp64 without contraction, every sum of three products as
+ * (a + b) + c.  For each point i in input order: its min(k, n) - 1 nearest others by (d2, index);
+ * up = the unit axis of the smallest |n_i| component (ties x, then y, then z), u = normalize(n_i x up)
+ * (a zero vector stays zero), v = n_i x u; a neighbour j is valid unless d2 > max_edge^2 or
+ * |n_i . n_j| < normal_thresh; with at least 2 valid neighbours they are sorted by
+ * angle = atan2(d . v, d . u), d = p_j - p_i, and each cyclically consecutive pair (b, c) gives the
+ * triangle (i, b, c) unless its gap (+ 2 pi on the wrap) is > max_ang_gap or |p_b - p_c|^2 >
+ * 2.5 max_edge^2; exactly 2 valid neighbours are visited as (0, 1) and (1, 0), as the reference does.
+ * Triangles are listed by centre point, then by fan position: the reference's order.  n < 3: none.
+ * Defined here and not by the reference: equal angles are ordered by position in the neighbour list
+ * (std::sort leaves it open); the list is the k - 1 nearest others, where the reference searches k
+ * including the point and skips it by index (the same list unless k or more exact duplicates of a
+ * point precede it in the input); atan2 is the device's, so a decision can differ from glibc's only
+ * where two angles of one fan, a gap and max_ang_gap, or a d2, dot or edge and its threshold agree to
+ * ~1e-9.  A zero normal gives its point no triangles.  Non-finite input is unsupported.
+ * use_grid: the search runs on the cell grid (n <= VS_CLOUD_GRID_MAX_POINTS instead of
+ * VS_CLOUD_MAX_POINTS; the same lists, hence the same triangles).  One call per context at a time. */
+typedef struct vs_cloud_mesh_config {
+    int k;                                         /* 20; 2 <= k <= VS_CLOUD_MAX_K */
+    double max_edge, normal_thresh, max_ang_gap;   /* 0.12, 0.5, 1.2 */
+    int use_grid;                                  /* 0 */
+} vs_cloud_mesh_config;
+void vs_cloud_mesh_default_config(vs_cloud_mesh_config* cfg);
+/* d_pts, d_normals [n][3] (the caller's normals, as in the reference); d_tri [cap][3] int32 indices
+ * into the input; d_counts [2] = {triangles, points with at least one triangle}.  When the triangles
+ * exceed cap the first cap are written and the total is still reported.  cfg NULL = the reference's
+ * values.  k < 2, max_edge <= 0 or a NULL normals pointer: VS_ERR_ARG; k > VS_CLOUD_MAX_K or n above
+ * the search's limit: VS_ERR_CAPACITY, before anything is allocated or read.  Enqueue only. */
+int vs_cloud_mesh_dev(vs_ctx* ctx, const double* d_pts, const double* d_normals, int n, const vs_cloud_mesh_config* cfg,
+                      int cap, int* d_tri, int* d_counts, void* stream);
+/* The same on host buffers; synchronous.  normals NULL: vs_cloud_normals (use_grid: _grid) with
+ * k = 20 runs first, the chain of main.cpp:1379-1415.  Optional outputs (each nullable): normals_out
+ * [n][3], the normals that were used; tri_verts / tri_normals [min(cap, triangles)][3][3], the
+ * reference's vertex and normal triples, gathered on the host from the index list. */
+int vs_cloud_mesh(vs_ctx* ctx, const double* pts, const double* normals, int n, const vs_cloud_mesh_config* cfg, int cap,
+                  int* tri, int counts[2], double* normals_out, double* tri_verts, double* tri_normals);
+
 /* ---- F4: Optimizer::pose_graph_optimize (Optimizer.cpp:654-863), g2o LM restated -------------
  * N keyframe poses (camera -> world, R [N][9] row-major, t [N][3], keyframe order; the first is
  * fixed), odometry edges between consecutive keyframes from these poses, L loop constraints

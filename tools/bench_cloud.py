@@ -11,6 +11,10 @@ holes cut into the planes, and a second pass with the context's stage profile on
 --grid times the cell-grid entry points (vs_cloud_knn_grid_dev, vs_cloud_normals_grid_dev with k = 20,
 vs_cloud_filter_grid_dev) beside their brute-force counterparts in the same run, then alone at 2^20 points, and
 reports the stats pair and each kernel's share and time per launch from a profile pass of its own.
+    python tools/bench_cloud.py --mesh [--out profiles/cloud_mesh.json]
+
+--mesh times vs_cloud_mesh_dev on --densify's cloud with precomputed normals, brute force and grid, then on the grid
+at 2^20 points, beside vs_cloud_normals[_grid]_dev at the same n, and each kernel's share from a profile pass.
 
 Pair tests per filter call = n0^2 + n1^2 (n0 points enter statistical_outlier_removal, n1 enter
 surface_aware_filter: every query meets every candidate).  One pair test is 3 sub, 3 mul, 2 add and
@@ -125,6 +129,43 @@ def grid_runs(ctx, args, cfg, stream, dev):
     return runs
 
 
+def mesh_runs(ctx, sizes, stream, dev):
+    s, runs = stream.cuda_stream, []
+    for n0 in sizes + [1 << 20]:
+        p = torch.from_numpy(np.ascontiguousarray(holed(cloud(n0)))).to(dev)
+        n, cap = p.shape[0], p.shape[0] * 19
+        nrm = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        scratch = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        tri = torch.zeros((cap, 3), dtype=torch.int32, device=dev)
+        cnt = torch.zeros(2, dtype=torch.int32, device=dev)
+        run = {"n_before_holes": n0, "n": n, "reps_per_round": {}}
+        for g in ([False, True] if n <= (1 << 18) else [True]):
+            cfg = ctx.mesh_config(grid=g)
+            ctx.cloud_normals_dev(p.data_ptr(), n, 20, nrm.data_ptr(), None, s, grid=g)  # precomputed: not timed
+            mesh = lambda: ctx.cloud_mesh_dev(p.data_ptr(), nrm.data_ptr(), n, cfg, cap, tri.data_ptr(),  # noqa: E731
+                                              cnt.data_ptr(), s)
+            normals = lambda: ctx.cloud_normals_dev(p.data_ptr(), n, 20, scratch.data_ptr(), None, s, grid=g)  # noqa: E731
+            reps = max(3, min(100, int((2e7 if g else 2e10 / n) / n)))
+            key = "_grid" if g else ""
+            for name, call in (("mesh", mesh), ("normals", normals)):
+                ms = timed(call, stream, 5, reps)
+                run[name + key + "_ms_rounds"], run[name + key + "_ms"] = ms, float(np.median(ms))
+            run["reps_per_round"]["mesh" + key] = reps
+            ctx.profile(True)  # a pass of its own: the stage events are not part of the timed calls above
+            ctx.profile_reset()
+            for _ in range(5):
+                mesh()
+            torch.cuda.synchronize()
+            prof = {k: v for k, v in ctx.profile_read().items() if v[1] > 0}  # the stages this path launched
+            ctx.profile(False)
+            tot = sum(ms for ms, _ in prof.values()) or 1.0
+            run["mesh" + key + "_kernel_share"] = {k: ms / tot for k, (ms, _) in prof.items()}
+            run["mesh" + key + "_kernel_ms_per_launch"] = {k: ms / max(c, 1) for k, (ms, c) in prof.items()}
+            run["counts" + key] = cnt.cpu().numpy().tolist()
+        runs.append(run)
+    return runs
+
+
 def timed(fn, stream, warm, reps, rounds=5):
     """ms per call: events on the stream the calls are enqueued on, around reps calls, per round."""
     for _ in range(warm):
@@ -149,6 +190,7 @@ def main():
     ap.add_argument("--k", type=int, default=25)
     ap.add_argument("--densify", action="store_true")
     ap.add_argument("--grid", action="store_true")
+    ap.add_argument("--mesh", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     cus = torch.cuda.get_device_properties(0).multi_processor_count
@@ -160,6 +202,8 @@ def main():
             res = {"device": res["device"], "cus": cus, "runs": densify_runs(ctx, args.sizes, stream, dev)}
         elif args.grid:
             res["runs"] = grid_runs(ctx, args, cfg, stream, dev)
+        elif args.mesh:
+            res = {"device": res["device"], "cus": cus, "runs": mesh_runs(ctx, args.sizes, stream, dev)}
         else:
             res["runs"] = filter_runs(ctx, args, cfg, cus, stream, dev)
     line = json.dumps(res)

@@ -353,9 +353,11 @@ void launch_knn(const CloudScratch& cs, const double* d_pts, const int* d_n, int
                        n_max, k, skip_small, cs.part_d2, cs.part_idx);
 }
 
-// the single list [k][n] of a grid search as vs_cloud_knn_dev's [n][k] output (k_cloud_reduce's list mode)
-int cloud_knn_lists(const CloudScratch& cs, const double* d_pts, int n, int k, int* d_nbr, double* d_d2, hipStream_t s) {
-    ReduceArgs r{d_pts, nullptr, n, k, 1, kReduceKnn, cs.part_d2, cs.part_idx, 0.0, nullptr, nullptr, d_nbr, d_d2};
+// the partial lists [S][k][n] (S = 1: a grid search's single list) as vs_cloud_knn_dev's [n][k] output
+// (k_cloud_reduce's list mode)
+int cloud_knn_lists(const CloudScratch& cs, const double* d_pts, int n, int k, int* d_nbr, double* d_d2, hipStream_t s,
+                    int S) {
+    ReduceArgs r{d_pts, nullptr, n, k, S, kReduceKnn, cs.part_d2, cs.part_idx, 0.0, nullptr, nullptr, d_nbr, d_d2};
     hipLaunchKernelGGL(k_cloud_reduce, dim3((n + kKnnLanes - 1) / kKnnLanes), dim3(kKnnLanes), 0, s, r);
     VS_HIP(hipGetLastError());
     return VS_OK;

@@ -32,7 +32,9 @@ void launch_knn(const CloudScratch& cs, const double* d_pts, const int* d_n, int
 // by the rings, by the full scan.  The grid's own scratch is the context's (cloud_grid), sized here.
 int launch_knn_grid(vs_ctx* ctx, const CloudScratch& cs, const double* d_pts, const int* d_n, int n_max, int k,
                     int skip_small, double cell_edge, int max_rings, int* d_stats, hipStream_t s);
-int cloud_knn_lists(const CloudScratch& cs, const double* d_pts, int n, int k, int* d_nbr, double* d_d2, hipStream_t s);
+// the S partial lists merged into vs_cloud_knn_dev's [n][k] output (k_cloud_reduce's list mode)
+int cloud_knn_lists(const CloudScratch& cs, const double* d_pts, int n, int k, int* d_nbr, double* d_d2, hipStream_t s,
+                    int S = 1);
 // VS_ERR_CAPACITY (and the message) when n or k is above what the search holds; called once per entry path
 int cloud_size_check(const char* who, int n, int k, int max_points = VS_CLOUD_MAX_POINTS);
 // the host-buffer calls behind vs_cloud_filter / vs_cloud_filter_grid and vs_cloud_normals / vs_cloud_normals_grid

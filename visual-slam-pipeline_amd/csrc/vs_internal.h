@@ -140,6 +140,7 @@ struct vs_ctx {
     int cloud_cus = 0;  // the device's CU count (k_cloud_knn's candidate split), read on first use
     vs::DevBuf densify;  // densify.hip: merged neighbour lists, normals, cell grid, candidates, voxel table
     vs::DevBuf cloud_grid;  // cloud_grid.hip: the k-NN's cell grid (sorted points, bucket table), its lists and state
+    vs::DevBuf cloud_mesh;  // cloud_mesh.hip: merged neighbour lists, the fans' sorted indices, masks and offsets
 
     bool prof_on = false;
     int prof_mode = 0;  // 1: every stage, 2: extraction stages only (vs_profile_enable)

@@ -123,6 +123,9 @@ _SIG = {
     "vs_cloud_normals": (_I, [_P, _P, _I, _I, _P, _P]),
     "vs_cloud_densify_dev": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _P]),
     "vs_cloud_densify": (_I, [_P, _P, _I, _P, _I, _P, _P, _P]),
+    "vs_cloud_mesh_default_config": (None, [_P]),
+    "vs_cloud_mesh_dev": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P]),
+    "vs_cloud_mesh": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
     "vs_slam_loops": (_I, [_P, _I, _P, _P, _P, _P]),
     "vs_pose_graph_optimize": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, ctypes.c_double, _I, _P, _P]),
     "vs_pgo_transform_points": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P]),
@@ -626,6 +629,43 @@ class Context:
         m = min(cap, int(counts[2]))
         return out[:m], src[:m], counts
 
+    # ---- the fan triangulation (main.cpp:689-774) ----
+    def mesh_config(self, grid=False, **overrides):
+        """vs_cloud_mesh_config with the reference's values (k 20, max_edge 0.12, normal_thresh 0.5, max_ang_gap 1.2)."""
+        cfg = CloudMeshConfig()
+        self.lib.vs_cloud_mesh_default_config(ctypes.byref(cfg))
+        cfg.use_grid = int(grid)
+        for k, v in overrides.items():
+            setattr(cfg, k, v)
+        return cfg
+
+    def cloud_mesh_dev(self, d_pts, d_normals, n, cfg, cap, d_tri, d_counts, stream=None):
+        """Device pointers; cfg a CloudMeshConfig or None (the reference's values).  Enqueue only."""
+        _check(self.lib.vs_cloud_mesh_dev(self.h, d_pts, d_normals, n, None if cfg is None else ctypes.byref(cfg), cap,
+                                          d_tri, d_counts, stream))
+
+    def cloud_mesh(self, pts, normals=None, grid=False, cap=None, gather=False, **cfg):
+        """Host points [n, 3] and their normals -> (tri [min(cap, T), 3] i32 indices into pts, counts [2] = triangles
+        T, points with a triangle).  normals None: estimated first with k = 20 and returned as a third value.
+        grid: the searches run on the cell grid.  cap None: room for every fan.  gather: also the reference's
+        tri_verts / tri_normals [m, 3, 3] as the last two values.  cfg: vs_cloud_mesh_config fields."""
+        p = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        n = p.shape[0]
+        c = self.mesh_config(grid, **cfg)
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float64).reshape(n, 3)
+        if cap is None:
+            cap = n * max(c.k - 1, 0)
+        tri = np.zeros((max(cap, 1), 3), np.int32)
+        counts = np.zeros(2, np.int32)
+        used = np.zeros((max(n, 1), 3)) if nrm is None else None
+        verts, vnrm = (np.zeros((max(cap, 1), 3, 3)), np.zeros((max(cap, 1), 3, 3))) if gather else (None, None)
+        opt = lambda a: None if a is None else _ptr(a)  # noqa: E731
+        _check(self.lib.vs_cloud_mesh(self.h, _ptr(p), opt(nrm), n, ctypes.byref(c), cap, _ptr(tri), _ptr(counts),
+                                      opt(used), opt(verts), opt(vnrm)))
+        m = min(cap, int(counts[0]))
+        res = (tri[:m], counts) + (() if used is None else (used[:n],))
+        return res + ((verts[:m], vnrm[:m]) if gather else ())
+
     # ---- profiling ----
     def spcf_write_dev(self, path, frame_idx, F, d_kps, d_desc, d_n, cap, append=False, stream=None):
         """vs_extract_batch_dev outputs (device pointers) -> SPCF entries frame_idx[f]."""
@@ -855,6 +895,12 @@ class CloudFilterConfig(ctypes.Structure):
 class CloudDensifyConfig(ctypes.Structure):
     """vs_cloud_densify_config (Context.densify_config fills in the reference's values)."""
     _fields_ = [("search_radius", ctypes.c_double), ("fill_step", ctypes.c_double), ("normal_thresh", ctypes.c_double)]
+
+
+class CloudMeshConfig(ctypes.Structure):
+    """vs_cloud_mesh_config (Context.mesh_config fills in the reference's values)."""
+    _fields_ = [("k", ctypes.c_int), ("max_edge", ctypes.c_double), ("normal_thresh", ctypes.c_double),
+                ("max_ang_gap", ctypes.c_double), ("use_grid", ctypes.c_int)]
 
 
 # ---- F4: dense voxel fusion (main.cpp:1081-1146) ----------------------------------------------
