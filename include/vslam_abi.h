@@ -642,6 +642,88 @@ int vs_cloud_mesh_dev(vs_ctx* ctx, const double* d_pts, const double* d_normals,
 int vs_cloud_mesh(vs_ctx* ctx, const double* pts, const double* normals, int n, const vs_cloud_mesh_config* cfg, int cap,
                   int* tri, int counts[2], double* normals_out, double* tri_verts, double* tri_normals);
 
+/* ---- Poisson surface reconstruction of the cloud (main.cpp:1379-1458 --poisson; csrc/cloud_poisson.hip) ----
+ * The reference writes points + normals to a file and runs PoissonRecon --depth 8 and SurfaceTrimmer on
+ * it.  PoissonRecon's adaptive octree, B-spline bases and screening are not restated: the semantics are
+ * defined here, on a dense grid, and every check is against a numpy fp64 restatement of this text.
+ * All arithmetic is fp64 without contraction, sums of three products as (a + b) + c.
+ * 0. Orientation (optional).  For point i, c = the view with the smallest (d2, index), d = c - p_i,
+ *    d2 = (dx dx + dy dy) + dz dz; the normal is negated when (nx dx + ny dy) + nz dz < 0.
+ * 1. Grid.  R = resolution nodes per axis (any integer, VS_POISSON_MIN_RES <= R <= VS_POISSON_MAX_RES).
+ *    lo, hi = the points' bounding box, side = scale * max(hi - lo), h = side / (R - 1),
+ *    o = (lo + hi) / 2 - side / 2.  Node (i, j, k) lies at o + h (i, j, k); its linear index is
+ *    (k R + j) R + i.  scale <= 1 or side == 0: VS_ERR_ARG.
+ * 2. Splat.  g = (p - o) / h per axis, b = floor(g) (kept inside [0, R - 2], which changes nothing unless
+ *    rounding puts g on the last node), f = g - b.  Node b + (dx, dy, dz) receives w n with
+ *    w = (wx wy) wz, w_axis = f when the offset is 1 and 1 - f when it is 0.  A node's sum runs over its
+ *    adjacent base cells in the order of the offset dx + 2 dy + 4 dz = 0 .. 7 from the cell to the node,
+ *    and over a cell's points in ascending index: V is the same bits from run to run.
+ * 3. div[i,j,k] = ((Vx[i+1] - Vx[i-1]) + (Vy[j+1] - Vy[j-1]) + (Vz[k+1] - Vz[k-1])) / (2 h), V = 0 outside.
+ * 4. A chi = -div with (A chi)[n] = (6 chi[n] - s) / (h h), s = the neighbours added in the order x-, x+,
+ *    y-, y+, z-, z+, chi = 0 outside.  Unpreconditioned conjugate gradients from x = 0: q = A p,
+ *    alpha = rho / (p.q), x += alpha p, r -= alpha q, rho' = r.r; stop when sqrt(rho') <= tol |rhs|_2 or
+ *    after max_iter iterations; else beta = rho' / rho, p = r + beta p.  A zero right-hand side: zero
+ *    iterations, chi = 0, no triangles.  Every dot product is summed in a fixed order, so the iteration
+ *    count and chi are the same bits from run to run.
+ * 5. iso = the mean over the points of chi interpolated at the point with step 2's weights (the eight
+ *    terms added in offset order, the points' values in a fixed order).
+ * 6. Extraction (also vs_grid_isosurface*, for any field): marching tetrahedra on the Kuhn subdivision.
+ *    Node n is below when field[n] < iso.  In the cube with base node (i, j, k) <= R - 2, tetrahedron
+ *    t = 0 .. 5 belongs to the axis order xyz, xzy, yxz, yzx, zxy, zyx: v0 = base, v1 = v0 + e_1st,
+ *    v2 = v1 + e_2nd, v3 = base + (1, 1, 1).  A tetrahedron edge runs from a node a to a + d,
+ *    d in {100, 010, 001, 110, 101, 011, 111} = kind 0 .. 6 ((dx, dy, dz) in that order).  Each edge with
+ *    exactly one end below carries a vertex: key 7 lin(a) + kind, id = the rank of its key, position
+ *    pa + t (pb - pa) per axis with pa = o + h i, pb = o + h (i + d), t = (iso - fa) / (fb - fa).
+ *    A tetrahedron with one vertex s alone on its side gives one triangle over the edges from s to the
+ *    other three in ascending order; with a < b below and c < d above, the triangles (ac, ad, bd) and
+ *    (ac, bd, bc).  A triangle keeps this order when, on the doubled edge midpoints (integers),
+ *    ((m1 - m0) x (m2 - m0)) . (nb sum of the above corners - na sum of the below corners) > 0 (na, nb:
+ *    the tetrahedron's vertices above and below), else its second and third vertex are swapped: its normal
+ *    points from below to above, for Poisson along the input normals.  It is then rotated so that its
+ *    smallest id comes first.  Triangles are listed by cube linear index, tetrahedron, and the pair's
+ *    first and second.  The mesh is closed wherever the surface does not reach the grid's boundary.
+ * Non-finite input is unsupported.  One call per context at a time; the scratch (40 R^3 bytes + 24 n for
+ * vs_cloud_poisson*, 9 R^3 for vs_grid_isosurface*) lives in the context. */
+#define VS_POISSON_MIN_RES 16
+#define VS_POISSON_MAX_RES 512
+#define VS_POISSON_MAX_VIEWS 65536
+typedef struct vs_cloud_poisson_config {
+    int resolution;      /* 256: PoissonRecon --depth 8 */
+    double scale, tol;   /* 1.1 (PoissonRecon's default), 1e-6 */
+    int max_iter;        /* 0 = 8 * resolution */
+} vs_cloud_poisson_config;
+void vs_cloud_poisson_default_config(vs_cloud_poisson_config* cfg);
+/* Step 0 in place on d_normals [n][3]; d_views [m][3].  m < 1: VS_ERR_ARG; m > VS_POISSON_MAX_VIEWS:
+ * VS_ERR_CAPACITY.  Enqueue only. */
+int vs_cloud_orient_normals_dev(vs_ctx* ctx, const double* d_pts, double* d_normals, int n, const double* d_views, int m,
+                                void* stream);
+/* The same on host buffers; synchronous. */
+int vs_cloud_orient_normals(vs_ctx* ctx, const double* pts, double* normals, int n, const double* views, int m);
+/* Step 6 on a device field [R^3] (2 <= R <= VS_POISSON_MAX_RES; origin on the host).  d_verts [vcap][3],
+ * d_tri [tcap][3] int32 vertex ids, d_counts [2] = {vertices, triangles}; above a cap the first cap
+ * entries are written and the totals are still reported.  h <= 0: VS_ERR_ARG.  Enqueue only. */
+int vs_grid_isosurface_dev(vs_ctx* ctx, const double* d_field, int resolution, const double origin[3], double h,
+                           double iso, int vcap, int tcap, double* d_verts, int* d_tri, int* d_counts, void* stream);
+/* The same on host buffers; synchronous. */
+int vs_grid_isosurface(vs_ctx* ctx, const double* field, int resolution, const double origin[3], double h, double iso,
+                       int vcap, int tcap, double* verts, int* tri, int counts[2]);
+/* Steps 1 - 6 on device points and oriented normals.  d_info [4] = {iterations, final sqrt(rho) / |rhs|,
+ * iso, converged}.  cfg NULL = the defaults.  Resolution below VS_POISSON_MIN_RES, scale <= 1, n < 1,
+ * tol < 0 or max_iter < 0: VS_ERR_ARG; resolution above VS_POISSON_MAX_RES or n above
+ * VS_CLOUD_GRID_MAX_POINTS: VS_ERR_CAPACITY, before anything is allocated or read.  The box is known
+ * only on the device: side == 0 is reported as d_info[3] = -1 with d_counts = {0, 0}.  max_iter
+ * iterations are enqueued; after the solver has stopped they return at once.  Enqueue only. */
+int vs_cloud_poisson_dev(vs_ctx* ctx, const double* d_pts, const double* d_normals, int n,
+                         const vs_cloud_poisson_config* cfg, int vcap, int tcap, double* d_verts, int* d_tri,
+                         int* d_counts, double* d_info, void* stream);
+/* The same on host buffers; synchronous (side == 0: VS_ERR_ARG).  views [m][3] non-NULL: step 0 runs
+ * first.  normals NULL: vs_cloud_normals with k = 20 runs first (main.cpp:1379), and views is then
+ * required (VS_ERR_ARG).  Optional outputs, each nullable: normals_out [n][3] the normals that were
+ * used, rhs_out [R^3] = div, field_out [R^3] = chi. */
+int vs_cloud_poisson(vs_ctx* ctx, const double* pts, const double* normals, int n, const double* views, int m,
+                     const vs_cloud_poisson_config* cfg, int vcap, int tcap, double* verts, int* tri, int counts[2],
+                     double info[4], double* normals_out, double* rhs_out, double* field_out);
+
 /* ---- F4: Optimizer::pose_graph_optimize (Optimizer.cpp:654-863), g2o LM restated -------------
  * N keyframe poses (camera -> world, R [N][9] row-major, t [N][3], keyframe order; the first is
  * fixed), odometry edges between consecutive keyframes from these poses, L loop constraints

@@ -16,6 +16,12 @@ reports the stats pair and each kernel's share and time per launch from a profil
 --mesh times vs_cloud_mesh_dev on --densify's cloud with precomputed normals, brute force and grid, then on the grid
 at 2^20 points, beside vs_cloud_normals[_grid]_dev at the same n, and each kernel's share from a profile pass.
 
+    python tools/bench_cloud.py --poisson [--out profiles/cloud_poisson.json]
+
+--poisson times vs_cloud_poisson_dev (normals precomputed with k = 20 and oriented towards a view inside the room) on
+--densify's cloud without its far outliers at R = 64, 128, 256, and reports the conjugate-gradient iterations and, from
+a profile pass of its own, each kernel's share and time per launch.
+
 Pair tests per filter call = n0^2 + n1^2 (n0 points enter statistical_outlier_removal, n1 enter
 surface_aware_filter: every query meets every candidate).  One pair test is 3 sub, 3 mul, 2 add and
 1 compare in fp64, none of them fused; the fp64 VALU peak used for the share is 78.6 TFLOP/s counting
@@ -166,6 +172,43 @@ def mesh_runs(ctx, sizes, stream, dev):
     return runs
 
 
+def poisson_runs(ctx, sizes, stream, dev):
+    s, runs = stream.cuda_stream, []
+    p = holed(cloud(sizes[-1]))
+    p = torch.from_numpy(np.ascontiguousarray(p[np.all(np.abs(p - 2.5) < 4.0, axis=1)])).to(dev)  # the room alone
+    n, vcap, tcap = p.shape[0], 1 << 22, 1 << 23
+    nrm = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+    view = torch.tensor([[2.0, 2.0, 2.0]], dtype=torch.float64, device=dev)
+    verts = torch.zeros((vcap, 3), dtype=torch.float64, device=dev)
+    tri = torch.zeros((tcap, 3), dtype=torch.int32, device=dev)
+    cnt = torch.zeros(2, dtype=torch.int32, device=dev)
+    info = torch.zeros(4, dtype=torch.float64, device=dev)
+    ctx.cloud_normals_dev(p.data_ptr(), n, 20, nrm.data_ptr(), None, s)
+    ctx.cloud_orient_normals_dev(p.data_ptr(), nrm.data_ptr(), n, view.data_ptr(), 1, s)
+    for R in (64, 128, 256):
+        cfg = ctx.poisson_config(resolution=R)
+        call = lambda: ctx.cloud_poisson_dev(p.data_ptr(), nrm.data_ptr(), n, cfg, vcap, tcap, verts.data_ptr(),  # noqa: E731
+                                             tri.data_ptr(), cnt.data_ptr(), info.data_ptr(), s)
+        reps = 2 if R > 128 else 5
+        ms = timed(call, stream, 1, reps)
+        ctx.profile(True)  # a pass of its own: the stage events are not part of the timed calls above
+        ctx.profile_reset()
+        call()
+        torch.cuda.synchronize()
+        prof = {k: v for k, v in ctx.profile_read().items() if v[1] > 0}
+        ctx.profile(False)
+        tot = sum(v[0] for v in prof.values()) or 1.0
+        it = info.cpu().numpy().tolist()
+        runs.append({"n": n, "resolution": R, "reps_per_round": reps, "poisson_ms_rounds": ms,
+                     "poisson_ms": float(np.median(ms)), "iterations": int(it[0]), "relative_residual": it[1],
+                     "iso": it[2], "converged": int(it[3]), "iterations_enqueued": 8 * R,
+                     "counts": cnt.cpu().numpy().tolist(),
+                     "kernel_share": {k: v[0] / tot for k, v in prof.items()},
+                     "kernel_ms_total": {k: v[0] for k, v in prof.items()},
+                     "kernel_launches": {k: v[1] for k, v in prof.items()}})
+    return runs
+
+
 def timed(fn, stream, warm, reps, rounds=5):
     """ms per call: events on the stream the calls are enqueued on, around reps calls, per round."""
     for _ in range(warm):
@@ -191,6 +234,7 @@ def main():
     ap.add_argument("--densify", action="store_true")
     ap.add_argument("--grid", action="store_true")
     ap.add_argument("--mesh", action="store_true")
+    ap.add_argument("--poisson", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     cus = torch.cuda.get_device_properties(0).multi_processor_count
@@ -202,6 +246,8 @@ def main():
             res = {"device": res["device"], "cus": cus, "runs": densify_runs(ctx, args.sizes, stream, dev)}
         elif args.grid:
             res["runs"] = grid_runs(ctx, args, cfg, stream, dev)
+        elif args.poisson:
+            res = {"device": res["device"], "cus": cus, "runs": poisson_runs(ctx, args.sizes, stream, dev)}
         elif args.mesh:
             res = {"device": res["device"], "cus": cus, "runs": mesh_runs(ctx, args.sizes, stream, dev)}
         else:

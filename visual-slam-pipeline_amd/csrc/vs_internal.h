@@ -141,6 +141,7 @@ struct vs_ctx {
     vs::DevBuf densify;  // densify.hip: merged neighbour lists, normals, cell grid, candidates, voxel table
     vs::DevBuf cloud_grid;  // cloud_grid.hip: the k-NN's cell grid (sorted points, bucket table), its lists and state
     vs::DevBuf cloud_mesh;  // cloud_mesh.hip: merged neighbour lists, the fans' sorted indices, masks and offsets
+    vs::DevBuf cloud_poisson;  // cloud_poisson.hip: five R^3 fp64 arrays, the point sort's buffers, partial sums and the state block
 
     bool prof_on = false;
     int prof_mode = 0;  // 1: every stage, 2: extraction stages only (vs_profile_enable)

@@ -126,6 +126,13 @@ _SIG = {
     "vs_cloud_mesh_default_config": (None, [_P]),
     "vs_cloud_mesh_dev": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P]),
     "vs_cloud_mesh": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "vs_cloud_poisson_default_config": (None, [_P]),
+    "vs_cloud_orient_normals_dev": (_I, [_P, _P, _P, _I, _P, _I, _P]),
+    "vs_cloud_orient_normals": (_I, [_P, _P, _P, _I, _P, _I]),
+    "vs_grid_isosurface_dev": (_I, [_P, _P, _I, _P, ctypes.c_double, ctypes.c_double, _I, _I, _P, _P, _P, _P]),
+    "vs_grid_isosurface": (_I, [_P, _P, _I, _P, ctypes.c_double, ctypes.c_double, _I, _I, _P, _P, _P]),
+    "vs_cloud_poisson_dev": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "vs_cloud_poisson": (_I, [_P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vs_slam_loops": (_I, [_P, _I, _P, _P, _P, _P]),
     "vs_pose_graph_optimize": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, ctypes.c_double, _I, _P, _P]),
     "vs_pgo_transform_points": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P]),
@@ -666,6 +673,75 @@ class Context:
         res = (tri[:m], counts) + (() if used is None else (used[:n],))
         return res + ((verts[:m], vnrm[:m]) if gather else ())
 
+    # ---- Poisson surface reconstruction (main.cpp:1379-1458 --poisson; the semantics are vslam_abi.h's) ----
+    def poisson_config(self, **overrides):
+        """vs_cloud_poisson_config with the defaults (resolution 256, scale 1.1, tol 1e-6, max_iter 0 = 8 resolution)."""
+        cfg = CloudPoissonConfig()
+        self.lib.vs_cloud_poisson_default_config(ctypes.byref(cfg))
+        for k, v in overrides.items():
+            setattr(cfg, k, v)
+        return cfg
+
+    def cloud_orient_normals_dev(self, d_pts, d_normals, n, d_views, m, stream=None):
+        """Device pointers; the normals are oriented in place.  Enqueue only."""
+        _check(self.lib.vs_cloud_orient_normals_dev(self.h, d_pts, d_normals, n, d_views, m, stream))
+
+    def cloud_orient_normals(self, pts, normals, views):
+        """Host points, normals [n, 3] and views [m, 3] -> the normals, each turned towards its nearest view."""
+        p = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        nrm = np.array(normals, np.float64).reshape(len(p), 3)
+        v = np.ascontiguousarray(views, np.float64).reshape(-1, 3)
+        _check(self.lib.vs_cloud_orient_normals(self.h, _ptr(p), _ptr(nrm), len(p), _ptr(v), len(v)))
+        return nrm
+
+    def grid_isosurface_dev(self, d_field, resolution, origin, h, iso, vcap, tcap, d_verts, d_tri, d_counts, stream=None):
+        """Device pointers (origin: three host floats).  Enqueue only."""
+        o = np.ascontiguousarray(origin, np.float64).reshape(3)
+        _check(self.lib.vs_grid_isosurface_dev(self.h, d_field, resolution, _ptr(o), h, iso, vcap, tcap, d_verts, d_tri,
+                                               d_counts, stream))
+
+    def grid_isosurface(self, field, origin, h, iso, vcap=None, tcap=None):
+        """Host field [R, R, R] indexed [k, j, i] -> (verts [min(vcap, V), 3], tri [min(tcap, T), 3] i32 vertex ids,
+        counts [2] = V, T).  Caps None: room for every edge and tetrahedron that could carry one."""
+        f = np.ascontiguousarray(field, np.float64)
+        R = f.shape[0]
+        assert f.shape == (R, R, R)
+        o = np.ascontiguousarray(origin, np.float64).reshape(3)
+        vcap = 7 * R ** 3 if vcap is None else vcap
+        tcap = 12 * R ** 3 if tcap is None else tcap
+        verts, tri = np.zeros((max(vcap, 1), 3)), np.zeros((max(tcap, 1), 3), np.int32)
+        counts = np.zeros(2, np.int32)
+        _check(self.lib.vs_grid_isosurface(self.h, _ptr(f), R, _ptr(o), h, iso, vcap, tcap, _ptr(verts), _ptr(tri),
+                                           _ptr(counts)))
+        return verts[:min(vcap, counts[0])], tri[:min(tcap, counts[1])], counts
+
+    def cloud_poisson_dev(self, d_pts, d_normals, n, cfg, vcap, tcap, d_verts, d_tri, d_counts, d_info, stream=None):
+        """Device pointers; cfg a CloudPoissonConfig or None (the defaults).  Enqueue only."""
+        _check(self.lib.vs_cloud_poisson_dev(self.h, d_pts, d_normals, n, None if cfg is None else ctypes.byref(cfg), vcap,
+                                             tcap, d_verts, d_tri, d_counts, d_info, stream))
+
+    def cloud_poisson(self, pts, normals=None, views=None, vcap=1 << 20, tcap=1 << 21, fields=False, **cfg):
+        """Host points [n, 3], normals (None: estimated with k = 20) and views (None: the normals are taken as oriented)
+        -> dict(verts, tri, counts [2] = vertices, triangles, info [4] = iterations, relative residual, iso, converged,
+        normals = the normals used; with fields also rhs and chi [R, R, R] indexed [k, j, i]).  cfg:
+        vs_cloud_poisson_config fields."""
+        p = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        n = p.shape[0]
+        c = self.poisson_config(**cfg)
+        opt = lambda a: None if a is None else _ptr(a)  # noqa: E731
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float64).reshape(n, 3)
+        v = None if views is None else np.ascontiguousarray(views, np.float64).reshape(-1, 3)
+        R = c.resolution
+        cube = (R, R, R) if fields and 0 < R <= 512 else None
+        rhs, chi = (None, None) if cube is None else (np.zeros(cube), np.zeros(cube))
+        verts, tri = np.zeros((max(vcap, 1), 3)), np.zeros((max(tcap, 1), 3), np.int32)
+        counts, info, used = np.zeros(2, np.int32), np.zeros(4), np.zeros((max(n, 1), 3))
+        _check(self.lib.vs_cloud_poisson(self.h, _ptr(p), opt(nrm), n, opt(v), 0 if v is None else len(v),
+                                         ctypes.byref(c), vcap, tcap, _ptr(verts), _ptr(tri), _ptr(counts), _ptr(info),
+                                         _ptr(used), opt(rhs), opt(chi)))
+        return dict(verts=verts[:min(vcap, counts[0])], tri=tri[:min(tcap, counts[1])], counts=counts, info=info,
+                    normals=used[:n], rhs=rhs, chi=chi)
+
     # ---- profiling ----
     def spcf_write_dev(self, path, frame_idx, F, d_kps, d_desc, d_n, cap, append=False, stream=None):
         """vs_extract_batch_dev outputs (device pointers) -> SPCF entries frame_idx[f]."""
@@ -901,6 +977,12 @@ class CloudMeshConfig(ctypes.Structure):
     """vs_cloud_mesh_config (Context.mesh_config fills in the reference's values)."""
     _fields_ = [("k", ctypes.c_int), ("max_edge", ctypes.c_double), ("normal_thresh", ctypes.c_double),
                 ("max_ang_gap", ctypes.c_double), ("use_grid", ctypes.c_int)]
+
+
+class CloudPoissonConfig(ctypes.Structure):
+    """vs_cloud_poisson_config (Context.poisson_config fills in the defaults)."""
+    _fields_ = [("resolution", ctypes.c_int), ("scale", ctypes.c_double), ("tol", ctypes.c_double),
+                ("max_iter", ctypes.c_int)]
 
 
 # ---- F4: dense voxel fusion (main.cpp:1081-1146) ----------------------------------------------
