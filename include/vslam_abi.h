@@ -665,6 +665,18 @@ int vs_cloud_mesh(vs_ctx* ctx, const double* pts, const double* normals, int n, 
  *    after max_iter iterations; else beta = rho' / rho, p = r + beta p.  A zero right-hand side: zero
  *    iterations, chi = 0, no triangles.  Every dot product is summed in a fixed order, so the iteration
  *    count and chi are the same bits from run to run.
+ *    The direct solve (solver = VS_POISSON_SOLVER_DIRECT, and vs_grid_poisson_solve*; csrc/poisson_dst.hip): with
+ *    S[a][b] = sin(pi a b / (R + 1)), a, b = 1 .. R, A is diagonal in the sine basis, and
+ *      chi = (S x S x S) [ -(2 / (R + 1))^3 (S x S x S) div / lambda ],
+ *      lambda_kji = (2 / (h h)) ((e_k + e_j) + e_i),  e_m = 2 sin^2(pi m / (2 (R + 1))):
+ *    S is applied along i, then j, then k; t -> -(t / lambda) (2 / (R + 1))^3; S along k, then j, then i.  An
+ *    entry of S is the sine of pi p / (R + 1) with a b reduced modulo 2 (R + 1) in integers and folded to
+ *    p <= (R + 1) / 2 (the sign kept), evaluated in extended precision and rounded once: within 1 ulp, and
+ *    S[a][b] == S[b][a] bit for bit.  A sum over an axis adds index m in ascending order four at a time:
+ *    the matrix instruction's (x_m s_m, .. , x_{m+3} s_{m+3}) onto the running sum, in its own internal order and
+ *    rounding.  Everything else is fp64 without contraction.  There is no tol and no iteration count: the
+ *    report is the measured |A chi + div|_2 / |div|_2 (A as above, one plain pass, fixed-order sums), 0 for
+ *    a zero right-hand side, whose chi is 0.  chi is the same bits from run to run.
  * 5. iso = the mean over the points of chi interpolated at the point with step 2's weights (the eight
  *    terms added in offset order, the points' values in a fixed order).
  * 6. Extraction (also vs_grid_isosurface*, for any field): marching tetrahedra on the Kuhn subdivision.
@@ -683,14 +695,18 @@ int vs_cloud_mesh(vs_ctx* ctx, const double* pts, const double* normals, int n, 
  *    smallest id comes first.  Triangles are listed by cube linear index, tetrahedron, and the pair's
  *    first and second.  The mesh is closed wherever the surface does not reach the grid's boundary.
  * Non-finite input is unsupported.  One call per context at a time; the scratch (40 R^3 bytes + 24 n for
- * vs_cloud_poisson*, 9 R^3 for vs_grid_isosurface*) lives in the context. */
+ * vs_cloud_poisson*, 9 R^3 for vs_grid_isosurface*, 24 R^3 for vs_grid_poisson_solve*; the direct solve adds
+ * its table, at most 2.6 MB) lives in the context. */
 #define VS_POISSON_MIN_RES 16
 #define VS_POISSON_MAX_RES 512
 #define VS_POISSON_MAX_VIEWS 65536
+#define VS_POISSON_SOLVER_CG 0
+#define VS_POISSON_SOLVER_DIRECT 1
 typedef struct vs_cloud_poisson_config {
     int resolution;      /* 256: PoissonRecon --depth 8 */
     double scale, tol;   /* 1.1 (PoissonRecon's default), 1e-6 */
     int max_iter;        /* 0 = 8 * resolution */
+    int solver;          /* VS_POISSON_SOLVER_CG; _DIRECT: tol and max_iter are ignored; another value: VS_ERR_ARG */
 } vs_cloud_poisson_config;
 void vs_cloud_poisson_default_config(vs_cloud_poisson_config* cfg);
 /* Step 0 in place on d_normals [n][3]; d_views [m][3].  m < 1: VS_ERR_ARG; m > VS_POISSON_MAX_VIEWS:
@@ -707,8 +723,15 @@ int vs_grid_isosurface_dev(vs_ctx* ctx, const double* d_field, int resolution, c
 /* The same on host buffers; synchronous. */
 int vs_grid_isosurface(vs_ctx* ctx, const double* field, int resolution, const double origin[3], double h, double iso,
                        int vcap, int tcap, double* verts, int* tri, int counts[2]);
+/* Step 4's direct solve alone: A chi = -rhs on a device field [R^3] (2 <= R <= VS_POISSON_MAX_RES).  d_chi may
+ * equal d_rhs.  d_info [2] = {0, relative residual}.  h <= 0 or not finite: VS_ERR_ARG.  Enqueue only (the
+ * first call with a new R also uploads its table). */
+int vs_grid_poisson_solve_dev(vs_ctx* ctx, const double* d_rhs, int resolution, double h, double* d_chi, double* d_info,
+                              void* stream);
+/* The same on host buffers; synchronous.  chi may equal rhs. */
+int vs_grid_poisson_solve(vs_ctx* ctx, const double* rhs, int resolution, double h, double* chi, double info[2]);
 /* Steps 1 - 6 on device points and oriented normals.  d_info [4] = {iterations, final sqrt(rho) / |rhs|,
- * iso, converged}.  cfg NULL = the defaults.  Resolution below VS_POISSON_MIN_RES, scale <= 1, n < 1,
+ * iso, converged}; with the direct solver {0, the measured relative residual, iso, 1}.  cfg NULL = the defaults.  Resolution below VS_POISSON_MIN_RES, scale <= 1, n < 1,
  * tol < 0 or max_iter < 0: VS_ERR_ARG; resolution above VS_POISSON_MAX_RES or n above
  * VS_CLOUD_GRID_MAX_POINTS: VS_ERR_CAPACITY, before anything is allocated or read.  The box is known
  * only on the device: side == 0 is reported as d_info[3] = -1 with d_counts = {0, 0}.  max_iter

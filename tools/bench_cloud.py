@@ -19,8 +19,11 @@ at 2^20 points, beside vs_cloud_normals[_grid]_dev at the same n, and each kerne
     python tools/bench_cloud.py --poisson [--out profiles/cloud_poisson.json]
 
 --poisson times vs_cloud_poisson_dev (normals precomputed with k = 20 and oriented towards a view inside the room) on
---densify's cloud without its far outliers at R = 64, 128, 256, and reports the conjugate-gradient iterations and, from
-a profile pass of its own, each kernel's share and time per launch.
+--densify's cloud without its far outliers at R = 64, 128, 256 (--resolutions), and reports the conjugate-gradient
+iterations and, from a profile pass of its own, each kernel's share and time per launch and the solve's own time (the
+k_cg_* or k_dst_* kernels).  --solver direct selects the sine-transform solve (csrc/poisson_dst.hip); its passes are
+then set against the card's peaks: a pass moves 16 R^3 bytes and does 2 R^4 flop (the z pair twice that), against
+8 TB/s of HBM and 78.6 TFLOP/s of fp64 matrix arithmetic.
 
 Pair tests per filter call = n0^2 + n1^2 (n0 points enter statistical_outlier_removal, n1 enter
 surface_aware_filter: every query meets every candidate).  One pair test is 3 sub, 3 mul, 2 add and
@@ -172,7 +175,10 @@ def mesh_runs(ctx, sizes, stream, dev):
     return runs
 
 
-def poisson_runs(ctx, sizes, stream, dev):
+PEAK_HBM, PEAK_FP64_MATRIX = 8.0e12, 78.6e12
+
+
+def poisson_runs(ctx, sizes, stream, dev, solver, resolutions):
     s, runs = stream.cuda_stream, []
     p = holed(cloud(sizes[-1]))
     p = torch.from_numpy(np.ascontiguousarray(p[np.all(np.abs(p - 2.5) < 4.0, axis=1)])).to(dev)  # the room alone
@@ -185,8 +191,8 @@ def poisson_runs(ctx, sizes, stream, dev):
     info = torch.zeros(4, dtype=torch.float64, device=dev)
     ctx.cloud_normals_dev(p.data_ptr(), n, 20, nrm.data_ptr(), None, s)
     ctx.cloud_orient_normals_dev(p.data_ptr(), nrm.data_ptr(), n, view.data_ptr(), 1, s)
-    for R in (64, 128, 256):
-        cfg = ctx.poisson_config(resolution=R)
+    for R in resolutions:
+        cfg = ctx.poisson_config(resolution=R, solver=1 if solver == "direct" else 0)
         call = lambda: ctx.cloud_poisson_dev(p.data_ptr(), nrm.data_ptr(), n, cfg, vcap, tcap, verts.data_ptr(),  # noqa: E731
                                              tri.data_ptr(), cnt.data_ptr(), info.data_ptr(), s)
         reps = 2 if R > 128 else 5
@@ -199,9 +205,20 @@ def poisson_runs(ctx, sizes, stream, dev):
         ctx.profile(False)
         tot = sum(v[0] for v in prof.values()) or 1.0
         it = info.cpu().numpy().tolist()
-        runs.append({"n": n, "resolution": R, "reps_per_round": reps, "poisson_ms_rounds": ms,
+        solve = {k: v for k, v in prof.items() if k.startswith(("k_cg_", "k_dst_"))}
+        run = {"solver": solver, "solve_ms": sum(v[0] for v in solve.values())}
+        if solver == "direct":  # per transform pass: the z pair is one launch of two products
+            run["passes"] = {}
+            for k, v in solve.items():
+                if k in ("k_dst_i", "k_dst_j", "k_dst_z", "k_dst_zz"):
+                    sec, flop = v[0] / v[1] * 1e-3, (4.0 if k == "k_dst_zz" else 2.0) * R ** 4
+                    run["passes"][k] = {"ms_per_launch": v[0] / v[1], "tb_per_s": 16.0 * R ** 3 / sec / 1e12,
+                                        "tflop_per_s": flop / sec / 1e12,
+                                        "share_of_hbm_peak": 16.0 * R ** 3 / sec / PEAK_HBM,
+                                        "share_of_fp64_matrix_peak": flop / sec / PEAK_FP64_MATRIX}
+        runs.append({**run, "n": n, "resolution": R, "reps_per_round": reps, "poisson_ms_rounds": ms,
                      "poisson_ms": float(np.median(ms)), "iterations": int(it[0]), "relative_residual": it[1],
-                     "iso": it[2], "converged": int(it[3]), "iterations_enqueued": 8 * R,
+                     "iso": it[2], "converged": int(it[3]), "iterations_enqueued": 0 if solver == "direct" else 8 * R,
                      "counts": cnt.cpu().numpy().tolist(),
                      "kernel_share": {k: v[0] / tot for k, v in prof.items()},
                      "kernel_ms_total": {k: v[0] for k, v in prof.items()},
@@ -235,6 +252,8 @@ def main():
     ap.add_argument("--grid", action="store_true")
     ap.add_argument("--mesh", action="store_true")
     ap.add_argument("--poisson", action="store_true")
+    ap.add_argument("--solver", choices=["cg", "direct"], default="cg")
+    ap.add_argument("--resolutions", type=int, nargs="+", default=[64, 128, 256])
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     cus = torch.cuda.get_device_properties(0).multi_processor_count
@@ -247,7 +266,7 @@ def main():
         elif args.grid:
             res["runs"] = grid_runs(ctx, args, cfg, stream, dev)
         elif args.poisson:
-            res = {"device": res["device"], "cus": cus, "runs": poisson_runs(ctx, args.sizes, stream, dev)}
+            res = {"device": res["device"], "cus": cus, "runs": poisson_runs(ctx, args.sizes, stream, dev, args.solver, args.resolutions)}
         elif args.mesh:
             res = {"device": res["device"], "cus": cus, "runs": mesh_runs(ctx, args.sizes, stream, dev)}
         else:

@@ -676,6 +676,10 @@ int poisson_check(const char* who, vs_cloud_poisson_config& c, int n) {
         set_error(std::string(who) + ": no points, scale not above 1, or a negative tol or max_iter");
         return VS_ERR_ARG;
     }
+    if (c.solver != VS_POISSON_SOLVER_CG && c.solver != VS_POISSON_SOLVER_DIRECT) {
+        set_error(std::string(who) + ": solver is neither VS_POISSON_SOLVER_CG nor VS_POISSON_SOLVER_DIRECT");
+        return VS_ERR_ARG;
+    }
     if (c.max_iter == 0) c.max_iter = 8 * c.resolution;
     return cloud_size_check(who, n, 1, VS_CLOUD_GRID_MAX_POINTS);
 }
@@ -766,6 +770,14 @@ int cg_iterate(vs_ctx* ctx, Plan& pl, int from, int to, hipStream_t s) {
     return VS_OK;
 }
 
+// VS_POISSON_SOLVER_DIRECT: div in arr[3] -> chi in arr[0] by poisson_dst.hip's sine transforms, through arr[1] and
+// arr[2].  arr[0] still holds the splat's zeros when the cloud has no extent: the transforms then write nothing.
+int direct_solve(vs_ctx* ctx, Plan& pl, hipStream_t s) {
+    PsState* st = pl.a.st;
+    const DstState ds{&st->ok, &st->h, &st->rho, &st->rhs_norm, &st->converged};
+    return poisson_dst_enqueue(ctx, pl.a.arr[3], pl.a.arr[0], pl.a.arr[1], pl.a.arr[2], pl.a.R, 0.0, &ds, nullptr, s);
+}
+
 // chi in arr[0] -> iso, the mesh and the report
 int poisson_finish(vs_ctx* ctx, Plan& pl, int vcap, int tcap, double* d_verts, int* d_tri, int* d_counts,
                    double* d_info, hipStream_t s) {
@@ -837,6 +849,7 @@ void vs_cloud_poisson_default_config(vs_cloud_poisson_config* c) {
     c->scale = 1.1;       // PoissonRecon's --scale default
     c->tol = 1e-6;
     c->max_iter = 0;      // 8 * resolution
+    c->solver = VS_POISSON_SOLVER_CG;
 }
 
 int vs_cloud_orient_normals_dev(vs_ctx* ctx, const double* d_pts, double* d_normals, int n, const double* d_views, int m,
@@ -925,8 +938,12 @@ int vs_cloud_poisson_dev(vs_ctx* ctx, const double* d_pts, const double* d_norma
     Plan pl;
     VS_CHECK(poisson_plan(ctx, d_pts, d_normals, n, c, &pl));
     VS_CHECK(poisson_rhs(ctx, pl, s));
-    VS_CHECK(cg_start(ctx, pl, s));
-    VS_CHECK(cg_iterate(ctx, pl, 0, c.max_iter, s));
+    if (c.solver == VS_POISSON_SOLVER_DIRECT) {
+        VS_CHECK(direct_solve(ctx, pl, s));
+    } else {
+        VS_CHECK(cg_start(ctx, pl, s));
+        VS_CHECK(cg_iterate(ctx, pl, 0, c.max_iter, s));
+    }
     return poisson_finish(ctx, pl, vcap, tcap, d_verts, d_tri, d_counts, d_info, s);
 }
 
@@ -975,8 +992,9 @@ int vs_cloud_poisson(vs_ctx* ctx, const double* pts, const double* normals, int 
     VS_CHECK(poisson_plan(ctx, d_in, d_nrm, n, c, &pl));
     VS_CHECK(poisson_rhs(ctx, pl, s));
     if (rhs_out) VS_HIP(hipMemcpyAsync(rhs_out, pl.a.arr[3], pl.nodes * sizeof(double), hipMemcpyDeviceToHost, s));
-    VS_CHECK(cg_start(ctx, pl, s));
-    for (int it = 0; it < c.max_iter; it += kPoll) {
+    if (c.solver == VS_POISSON_SOLVER_DIRECT) VS_CHECK(direct_solve(ctx, pl, s));
+    else VS_CHECK(cg_start(ctx, pl, s));
+    for (int it = 0; it < c.max_iter && c.solver == VS_POISSON_SOLVER_CG; it += kPoll) {
         int done = 0;
         VS_HIP(hipMemcpyAsync(&done, &pl.a.st->done, sizeof(int), hipMemcpyDeviceToHost, s));
         VS_HIP(hipStreamSynchronize(s));

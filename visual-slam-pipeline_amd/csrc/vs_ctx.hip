@@ -452,7 +452,7 @@ void vs_destroy(vs_ctx* ctx) {
                       &ctx->h_desc, &ctx->h_n,   &ctx->h_aux0, &ctx->h_aux1, &ctx->h_aux2, &ctx->h_aux3,
                       &ctx->h_aux4, &ctx->h_aux5, &ctx->match_keys, &ctx->match_cnt, &ctx->nms_list, &ctx->norms_sets, &ctx->tlm, &ctx->ba, &ctx->pnp,
                       &ctx->pnp_tab, &ctx->em_tab, &ctx->em_sync, &ctx->fm_sync, &ctx->tie_totals, &ctx->cloud, &ctx->densify, &ctx->cloud_grid,
-                      &ctx->cloud_mesh, &ctx->cloud_poisson};
+                      &ctx->cloud_mesh, &ctx->cloud_poisson, &ctx->poisson_dst};
     for (DevBuf* b : bufs) b->release();
     for (auto& st : ctx->prof)
         for (auto& pr : st.pending) {

@@ -142,6 +142,8 @@ struct vs_ctx {
     vs::DevBuf cloud_grid;  // cloud_grid.hip: the k-NN's cell grid (sorted points, bucket table), its lists and state
     vs::DevBuf cloud_mesh;  // cloud_mesh.hip: merged neighbour lists, the fans' sorted indices, masks and offsets
     vs::DevBuf cloud_poisson;  // cloud_poisson.hip: five R^3 fp64 arrays, the point sort's buffers, partial sums and the state block
+    vs::DevBuf poisson_dst;  // poisson_dst.hip: the residual's partial sums, the sine table and the eigenvalue vector of ...
+    int poisson_dst_R = 0;   // ... this resolution (0: none yet)
 
     bool prof_on = false;
     int prof_mode = 0;  // 1: every stage, 2: extraction stages only (vs_profile_enable)
@@ -327,6 +329,19 @@ int cloud_normals(vs_ctx* ctx, const double* d_pts, int n_max, int k, double* d_
                   bool grid = false);
 int cloud_densify(vs_ctx* ctx, const double* d_pts, int n_max, const vs_cloud_densify_config& c,
                   int cap, double* d_out, int* d_src, int* d_counts, hipStream_t s);
+// The direct Poisson solve (poisson_dst.hip): A chi = -d_div on R^3 nodes by sine transforms, five or six passes through
+// the scratch fields t0 and t1 (R^3 each, apart from d_div and d_chi; d_div is read again by the residual pass after
+// d_chi is written, so the two differ).  st (nullable): cloud_poisson.hip's state block on the device — ok and h are read there, and
+// rho, rhs_norm and converged written as its report expects; without it h is the host's.  d_info (nullable) =
+// {0, relative residual}.  Enqueue only, but for the table's upload on the first call with a new R.
+struct DstState {
+    const int* ok;
+    const double* h;
+    double *rho, *rhs_norm;
+    int* converged;
+};
+int poisson_dst_enqueue(vs_ctx* ctx, const double* d_div, double* d_chi, double* t0, double* t1, int R, double h,
+                        const DstState* st, double* d_info, hipStream_t s);
 // Local bundle adjustment over a gathered window (host arrays in/out, see vs_local_ba)
 int local_ba(vs_ctx* ctx, int N, double* R, double* t, int M, double* P, int n_obs, const int* okf, const int* opt,
              const double* ouv, const double K4[4], int max_iter, double* err_before, double* err_after, int stats[3]);

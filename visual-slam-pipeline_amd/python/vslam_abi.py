@@ -131,6 +131,8 @@ _SIG = {
     "vs_cloud_orient_normals": (_I, [_P, _P, _P, _I, _P, _I]),
     "vs_grid_isosurface_dev": (_I, [_P, _P, _I, _P, ctypes.c_double, ctypes.c_double, _I, _I, _P, _P, _P, _P]),
     "vs_grid_isosurface": (_I, [_P, _P, _I, _P, ctypes.c_double, ctypes.c_double, _I, _I, _P, _P, _P]),
+    "vs_grid_poisson_solve_dev": (_I, [_P, _P, _I, ctypes.c_double, _P, _P, _P]),
+    "vs_grid_poisson_solve": (_I, [_P, _P, _I, ctypes.c_double, _P, _P]),
     "vs_cloud_poisson_dev": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "vs_cloud_poisson": (_I, [_P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vs_slam_loops": (_I, [_P, _I, _P, _P, _P, _P]),
@@ -675,7 +677,8 @@ class Context:
 
     # ---- Poisson surface reconstruction (main.cpp:1379-1458 --poisson; the semantics are vslam_abi.h's) ----
     def poisson_config(self, **overrides):
-        """vs_cloud_poisson_config with the defaults (resolution 256, scale 1.1, tol 1e-6, max_iter 0 = 8 resolution)."""
+        """vs_cloud_poisson_config with the defaults (resolution 256, scale 1.1, tol 1e-6, max_iter 0 = 8 resolution,
+        solver 0 = conjugate gradients; 1 = the direct solve by sine transforms)."""
         cfg = CloudPoissonConfig()
         self.lib.vs_cloud_poisson_default_config(ctypes.byref(cfg))
         for k, v in overrides.items():
@@ -714,6 +717,22 @@ class Context:
         _check(self.lib.vs_grid_isosurface(self.h, _ptr(f), R, _ptr(o), h, iso, vcap, tcap, _ptr(verts), _ptr(tri),
                                            _ptr(counts)))
         return verts[:min(vcap, counts[0])], tri[:min(tcap, counts[1])], counts
+
+    def grid_poisson_solve_dev(self, d_rhs, resolution, h, d_chi, d_info, stream=None):
+        """Device pointers; A chi = -rhs by the direct solve, d_chi may be d_rhs, d_info [2] fp64.  Enqueue only."""
+        _check(self.lib.vs_grid_poisson_solve_dev(self.h, d_rhs, resolution, h, d_chi, d_info, stream))
+
+    def grid_poisson_solve(self, rhs, h, out=None):
+        """Host field [R, R, R] indexed [k, j, i] -> (chi, info [2] = 0, relative residual).  out: a contiguous fp64
+        array for chi, which may be rhs itself (the solve then runs in place)."""
+        f = np.ascontiguousarray(rhs, np.float64)
+        R = f.shape[0]
+        assert f.shape == (R, R, R)
+        chi = np.zeros_like(f) if out is None else out
+        assert chi.shape == f.shape and chi.dtype == np.float64 and chi.flags.c_contiguous
+        info = np.zeros(2)
+        _check(self.lib.vs_grid_poisson_solve(self.h, _ptr(f), R, h, _ptr(chi), _ptr(info)))
+        return chi, info
 
     def cloud_poisson_dev(self, d_pts, d_normals, n, cfg, vcap, tcap, d_verts, d_tri, d_counts, d_info, stream=None):
         """Device pointers; cfg a CloudPoissonConfig or None (the defaults).  Enqueue only."""
@@ -982,7 +1001,7 @@ class CloudMeshConfig(ctypes.Structure):
 class CloudPoissonConfig(ctypes.Structure):
     """vs_cloud_poisson_config (Context.poisson_config fills in the defaults)."""
     _fields_ = [("resolution", ctypes.c_int), ("scale", ctypes.c_double), ("tol", ctypes.c_double),
-                ("max_iter", ctypes.c_int)]
+                ("max_iter", ctypes.c_int), ("solver", ctypes.c_int)]
 
 
 # ---- F4: dense voxel fusion (main.cpp:1081-1146) ----------------------------------------------
