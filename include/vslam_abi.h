@@ -658,6 +658,9 @@ int vs_cloud_mesh(vs_ctx* ctx, const double* pts, const double* normals, int n, 
  *    w = (wx wy) wz, w_axis = f when the offset is 1 and 1 - f when it is 0.  A node's sum runs over its
  *    adjacent base cells in the order of the offset dx + 2 dy + 4 dz = 0 .. 7 from the cell to the node,
  *    and over a cell's points in ascending index: V is the same bits from run to run.
+ * 2b. Density.  W[node] = sum of w over the points, with step 2's weights in step 2's cell and point order
+ *    (the splat's fourth sum): the same bits from run to run.  Computed only when point_weight > 0,
+ *    trim > 0 or a density output is asked for.
  * 3. div[i,j,k] = ((Vx[i+1] - Vx[i-1]) + (Vy[j+1] - Vy[j-1]) + (Vz[k+1] - Vz[k-1])) / (2 h), V = 0 outside.
  * 4. A chi = -div with (A chi)[n] = (6 chi[n] - s) / (h h), s = the neighbours added in the order x-, x+,
  *    y-, y+, z-, z+, chi = 0 outside.  Unpreconditioned conjugate gradients from x = 0: q = A p,
@@ -677,6 +680,23 @@ int vs_cloud_mesh(vs_ctx* ctx, const double* pts, const double* normals, int n, 
  *    rounding.  Everything else is fp64 without contraction.  There is no tol and no iteration count: the
  *    report is the measured |A chi + div|_2 / |div|_2 (A as above, one plain pass, fixed-order sums), 0 for
  *    a zero right-hand side, whose chi is 0.  chi is the same bits from run to run.
+ * 4s. Screened solve (point_weight > 0; csrc/poisson_screen.hip).  B is the n x R^3 matrix of step 2's
+ *    weights: (B chi)_p is chi interpolated at point p, its eight terms added in offset order.  chi0 = step
+ *    4's result with the configured solver; tau = step 5's mean of chi0 at the points; dbar = n / (the
+ *    number of base cells that hold a point, an integer count); lambda = point_weight / ((h h) dbar), so that
+ *    the setting means the same at every resolution and sampling density.  Then
+ *      (A + lambda B^T B) chi = b,  b = -div + (lambda tau) W,
+ *    by preconditioned conjugate gradients from x = chi0: r = b - (A x + lambda B^T (B x)) evaluated in full
+ *    (lambda B^T (tau 1 - B chi0) but for step 4's own residual), z = P r, p = z, then q = A p + lambda
+ *    B^T (B p), alpha = (r.z) / (p.q), x += alpha p, r -= alpha q; stop when sqrt(r.r) <= tol |b|_2 or after
+ *    max_iter iterations; else z = P r, beta = (r.z)' / (r.z), p = z + beta p.  P = A^-1 by step 4's sine
+ *    transforms when solver = VS_POISSON_SOLVER_DIRECT, and the identity (plain conjugate gradients through
+ *    the same loop) when solver = VS_POISSON_SOLVER_CG; tol and max_iter apply here with either solver
+ *    (max_iter 0 = 8 * resolution without the preconditioner, 192 with it).  (B^T s)[node] is summed in step
+ *    2's order and added as q = (A p) + lambda (B^T s) at the nodes with W != 0; every dot product is summed
+ *    in a fixed order: the iteration count and chi are the same bits from run to run.  r.r <= (tol |b|)^2
+ *    at the start (a zero b among them): zero iterations.  Step 5 then takes iso from the screened chi, and
+ *    info = {screened iterations, final sqrt(r.r) / |b|_2, iso, converged}.
  * 5. iso = the mean over the points of chi interpolated at the point with step 2's weights (the eight
  *    terms added in offset order, the points' values in a fixed order).
  * 6. Extraction (also vs_grid_isosurface*, for any field): marching tetrahedra on the Kuhn subdivision.
@@ -694,8 +714,15 @@ int vs_cloud_mesh(vs_ctx* ctx, const double* pts, const double* normals, int n, 
  *    points from below to above, for Poisson along the input normals.  It is then rotated so that its
  *    smallest id comes first.  Triangles are listed by cube linear index, tetrahedron, and the pair's
  *    first and second.  The mesh is closed wherever the surface does not reach the grid's boundary.
+ * 7. Trimming (trim > 0).  The vertex on the edge a -> b at step 6's t has density rho = W[a] + t (W[b] -
+ *    W[a]).  A vertex survives when rho >= trim; a triangle survives when its three vertices do.  Unlike
+ *    SurfaceTrimmer, no triangle is split along rho = trim: the border follows the mesh's edges.  Surviving
+ *    vertices keep their relative order and are renumbered by rank; surviving triangles keep step 6's order
+ *    and rotation; counts = {surviving vertices, surviving triangles}.  A surviving vertex that no surviving
+ *    triangle uses is kept: it is still a measured surface point.
  * Non-finite input is unsupported.  One call per context at a time; the scratch (40 R^3 bytes + 24 n for
- * vs_cloud_poisson*, 9 R^3 for vs_grid_isosurface*, 24 R^3 for vs_grid_poisson_solve*; the direct solve adds
+ * vs_cloud_poisson*, 48 R^3 with W (trimming or a density output), 60 R^3 + 56 n with screening — x, r, z,
+ * two p, q, W and the cells' starts; the preconditioner's transforms run through q and the idle p; 9 R^3 for vs_grid_isosurface*, 24 R^3 for vs_grid_poisson_solve*; the direct solve adds
  * its table, at most 2.6 MB) lives in the context. */
 #define VS_POISSON_MIN_RES 16
 #define VS_POISSON_MAX_RES 512
@@ -706,7 +733,9 @@ typedef struct vs_cloud_poisson_config {
     int resolution;      /* 256: PoissonRecon --depth 8 */
     double scale, tol;   /* 1.1 (PoissonRecon's default), 1e-6 */
     int max_iter;        /* 0 = 8 * resolution */
-    int solver;          /* VS_POISSON_SOLVER_CG; _DIRECT: tol and max_iter are ignored; another value: VS_ERR_ARG */
+    int solver;          /* VS_POISSON_SOLVER_CG; _DIRECT: tol and max_iter are ignored by step 4; another value: VS_ERR_ARG */
+    double point_weight; /* 0 = off: step 4s (PoissonRecon --pointWeight; the reference passes 6); < 0 or not finite: VS_ERR_ARG */
+    double trim;         /* 0 = off: step 7 (SurfaceTrimmer --trim), a threshold on W; < 0 or not finite: VS_ERR_ARG */
 } vs_cloud_poisson_config;
 void vs_cloud_poisson_default_config(vs_cloud_poisson_config* cfg);
 /* Step 0 in place on d_normals [n][3]; d_views [m][3].  m < 1: VS_ERR_ARG; m > VS_POISSON_MAX_VIEWS:
@@ -746,6 +775,19 @@ int vs_cloud_poisson_dev(vs_ctx* ctx, const double* d_pts, const double* d_norma
 int vs_cloud_poisson(vs_ctx* ctx, const double* pts, const double* normals, int n, const double* views, int m,
                      const vs_cloud_poisson_config* cfg, int vcap, int tcap, double* verts, int* tri, int counts[2],
                      double info[4], double* normals_out, double* rhs_out, double* field_out);
+/* vs_cloud_poisson_dev with one more output, nullable: d_vert_density [vcap] = step 7's rho of each written
+ * vertex (what PoissonRecon --density attaches).  vs_cloud_poisson_dev is this call with NULL.  With
+ * point_weight > 0 the screened loop's max_iter iterations are enqueued as step 4's are: no host round
+ * trip.  Enqueue only. */
+int vs_cloud_poisson_density_dev(vs_ctx* ctx, const double* d_pts, const double* d_normals, int n,
+                                 const vs_cloud_poisson_config* cfg, int vcap, int tcap, double* d_verts, int* d_tri,
+                                 int* d_counts, double* d_info, double* d_vert_density, void* stream);
+/* vs_cloud_poisson with two more outputs, each nullable: density_out [R^3] = W, vert_density
+ * [min(vcap, vertices)] = rho per vertex.  vs_cloud_poisson is this call with both NULL.  Synchronous. */
+int vs_cloud_poisson_density(vs_ctx* ctx, const double* pts, const double* normals, int n, const double* views, int m,
+                             const vs_cloud_poisson_config* cfg, int vcap, int tcap, double* verts, int* tri,
+                             int counts[2], double info[4], double* normals_out, double* rhs_out, double* field_out,
+                             double* density_out, double* vert_density);
 
 /* ---- F4: Optimizer::pose_graph_optimize (Optimizer.cpp:654-863), g2o LM restated -------------
  * N keyframe poses (camera -> world, R [N][9] row-major, t [N][3], keyframe order; the first is

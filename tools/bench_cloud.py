@@ -23,7 +23,11 @@ at 2^20 points, beside vs_cloud_normals[_grid]_dev at the same n, and each kerne
 iterations and, from a profile pass of its own, each kernel's share and time per launch and the solve's own time (the
 k_cg_* or k_dst_* kernels).  --solver direct selects the sine-transform solve (csrc/poisson_dst.hip); its passes are
 then set against the card's peaks: a pass moves 16 R^3 bytes and does 2 R^4 flop (the z pair twice that), against
-8 TB/s of HBM and 78.6 TFLOP/s of fp64 matrix arithmetic.
+8 TB/s of HBM and 78.6 TFLOP/s of fp64 matrix arithmetic.  --point-weight adds the screened solve (step 4s): its
+iterations, and from the profile pass (run with max_iter = the measured count under the preconditioner, so that no
+idle launch is averaged in) the time per iteration of the operator (k_sc_apply), the interpolation (k_sc_interp), the
+preconditioner (k_dst_*) and the updates (k_sc_update, k_sc_rz).  --trim adds step 7 and times the untrimmed call of
+the same settings beside it, rounds alternating.
 
 Pair tests per filter call = n0^2 + n1^2 (n0 points enter statistical_outlier_removal, n1 enter
 surface_aware_filter: every query meets every candidate).  One pair test is 3 sub, 3 mul, 2 add and
@@ -178,7 +182,7 @@ def mesh_runs(ctx, sizes, stream, dev):
 PEAK_HBM, PEAK_FP64_MATRIX = 8.0e12, 78.6e12
 
 
-def poisson_runs(ctx, sizes, stream, dev, solver, resolutions):
+def poisson_runs(ctx, sizes, stream, dev, solver, resolutions, point_weight=0.0, trim=0.0, max_iter=0):
     s, runs = stream.cuda_stream, []
     p = holed(cloud(sizes[-1]))
     p = torch.from_numpy(np.ascontiguousarray(p[np.all(np.abs(p - 2.5) < 4.0, axis=1)])).to(dev)  # the room alone
@@ -192,11 +196,26 @@ def poisson_runs(ctx, sizes, stream, dev, solver, resolutions):
     ctx.cloud_normals_dev(p.data_ptr(), n, 20, nrm.data_ptr(), None, s)
     ctx.cloud_orient_normals_dev(p.data_ptr(), nrm.data_ptr(), n, view.data_ptr(), 1, s)
     for R in resolutions:
-        cfg = ctx.poisson_config(resolution=R, solver=1 if solver == "direct" else 0)
-        call = lambda: ctx.cloud_poisson_dev(p.data_ptr(), nrm.data_ptr(), n, cfg, vcap, tcap, verts.data_ptr(),  # noqa: E731
-                                             tri.data_ptr(), cnt.data_ptr(), info.data_ptr(), s)
+        extra = {"point_weight": point_weight, "trim": trim} if point_weight or trim else {}  # the plain call: the config as it was
+        base = dict(resolution=R, solver=1 if solver == "direct" else 0, **({"point_weight": point_weight} if point_weight else {}),
+                    **({"max_iter": max_iter} if max_iter else {}))
+        enqueue = lambda c: ctx.cloud_poisson_dev(p.data_ptr(), nrm.data_ptr(), n, c, vcap, tcap, verts.data_ptr(),  # noqa: E731
+                                                  tri.data_ptr(), cnt.data_ptr(), info.data_ptr(), s)
+        cfg = ctx.poisson_config(**base, **({"trim": trim} if trim else {}))
+        call = lambda: enqueue(cfg)  # noqa: E731
         reps = 2 if R > 128 else 5
-        ms = timed(call, stream, 1, reps)
+        if trim:  # the untrimmed call of the same session, its rounds between the trimmed call's
+            untrimmed = ctx.poisson_config(**base)
+            pairs = [(timed(call, stream, 1, reps, 1)[0], timed(lambda: enqueue(untrimmed), stream, 1, reps, 1)[0]) for _ in range(5)]
+            ms, extra["untrimmed_ms_rounds"] = [a for a, _ in pairs], [b for _, b in pairs]
+            extra["untrimmed_ms"] = float(np.median(extra["untrimmed_ms_rounds"]))
+            call()
+        else:
+            ms = timed(call, stream, 1, reps)
+        torch.cuda.synchronize()
+        it = info.cpu().numpy().tolist()
+        if point_weight and solver == "direct":
+            cfg = ctx.poisson_config(**{**base, "max_iter": max(int(it[0]), 1)}, **({"trim": trim} if trim else {}))
         ctx.profile(True)  # a pass of its own: the stage events are not part of the timed calls above
         ctx.profile_reset()
         call()
@@ -204,9 +223,15 @@ def poisson_runs(ctx, sizes, stream, dev, solver, resolutions):
         prof = {k: v for k, v in ctx.profile_read().items() if v[1] > 0}
         ctx.profile(False)
         tot = sum(v[0] for v in prof.values()) or 1.0
-        it = info.cpu().numpy().tolist()
-        solve = {k: v for k, v in prof.items() if k.startswith(("k_cg_", "k_dst_"))}
-        run = {"solver": solver, "solve_ms": sum(v[0] for v in solve.values())}
+        solve = {k: v for k, v in prof.items() if k.startswith(("k_cg_", "k_dst_", "k_sc_"))}
+        run = {"solver": solver, "solve_ms": sum(v[0] for v in solve.values()), **extra}
+        if point_weight:
+            group = lambda *names: sum(v[0] for k, v in prof.items() if k.startswith(names))  # noqa: E731
+            its = max(int(it[0]), 1)
+            run["screened_ms_per_iteration"] = {
+                "apply": group("k_sc_apply") / (its + 1), "interp": group("k_sc_interp") / (its + 1),
+                "preconditioner": group("k_dst_") / (its + 2) if solver == "direct" else 0.0,
+                "updates": group("k_sc_update", "k_sc_rz") / its}
         if solver == "direct":  # per transform pass: the z pair is one launch of two products
             run["passes"] = {}
             for k, v in solve.items():
@@ -254,6 +279,9 @@ def main():
     ap.add_argument("--poisson", action="store_true")
     ap.add_argument("--solver", choices=["cg", "direct"], default="cg")
     ap.add_argument("--resolutions", type=int, nargs="+", default=[64, 128, 256])
+    ap.add_argument("--point-weight", type=float, default=0.0)
+    ap.add_argument("--trim", type=float, default=0.0)
+    ap.add_argument("--max-iter", type=int, default=0)
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     cus = torch.cuda.get_device_properties(0).multi_processor_count
@@ -266,7 +294,8 @@ def main():
         elif args.grid:
             res["runs"] = grid_runs(ctx, args, cfg, stream, dev)
         elif args.poisson:
-            res = {"device": res["device"], "cus": cus, "runs": poisson_runs(ctx, args.sizes, stream, dev, args.solver, args.resolutions)}
+            res = {"device": res["device"], "cus": cus, "runs": poisson_runs(ctx, args.sizes, stream, dev, args.solver, args.resolutions,
+                                                                             args.point_weight, args.trim, args.max_iter)}
         elif args.mesh:
             res = {"device": res["device"], "cus": cus, "runs": mesh_runs(ctx, args.sizes, stream, dev)}
         else:

@@ -37,40 +37,31 @@
 // Memory: five arrays of R^3 fp64 (V's three, div, one more) become x, the two p buffers, r and q; the cells' starts
 // and the extraction's mask and offsets live inside arrays that are dead at the time: 40 R^3 bytes (+ 24 n for the
 // point sort): 0.67 GB at R = 256, 5.4 GB at R = 512.  No MFMA: an fp64 7-point stencil has no matrix product in it.
+// Steps 2b, 4s and 7 (point_weight, trim, the density outputs) are template variants here — k_ps_gather<true> (W and
+// the occupied cells), k_iso_mask / k_iso_verts / k_iso_tris<true> — and poisson_screen.hip's loop; W is a sixth array,
+// screening a seventh and the cells' starts apart (poisson_plan).  With both settings 0 none of them is launched.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-#include "block_reduce.h"
-#include "cloud_common.h"
+#include "poisson_common.h"
 
 namespace vs {
 
 namespace {
 
-constexpr int kTX = 32, kTY = 8, kZChunk = 32;  // k_cg_apply's column of nodes and its planes per workgroup
-constexpr int kHalo = 2 * kTX + 2 * kTY;         // the plane's halo ring without its corners
-constexpr int kTile = 4096;                      // entries per workgroup of the scan and of k_cg_update
-constexpr int kMaxTiles = 32 * 1024;             // 512^3 / kTile; k_scan_top holds 32 per lane
 constexpr int kBoxBlocks = 256;
 constexpr int kRsBits = 9, kRsBins = 1 << kRsBits;  // the point sort's digit
 constexpr int kPoll = 64;                        // the host call reads the stop flag every kPoll iterations
+constexpr int kScPoll = 8;                       // ... and every kScPoll of the screened loop's preconditioned ones
+constexpr int kScIters = 192;                    // max_iter = 0 for the preconditioned screened loop: twice the 92 measured
 constexpr int kNormalK = 20;                     // main.cpp:1379
-static_assert(kHalo <= 256 && kTX * kTY == 256, "one halo node per lane");
 static_assert((size_t)VS_POISSON_MAX_RES * VS_POISSON_MAX_RES * VS_POISSON_MAX_RES <= (size_t)kMaxTiles * kTile,
               "k_scan_top's tile sums");
 static_assert(12ll * VS_POISSON_MAX_RES * VS_POISSON_MAX_RES * VS_POISSON_MAX_RES < (1ll << 31), "32-bit offsets");
 static_assert(VS_CLOUD_GRID_MAX_POINTS / 256 <= kMaxTiles, "k_ps_iso's partials");
-
-// the state block on the device
-struct PsState {
-    double o[3], h;                          // the grid
-    double rho, alpha, beta, rhs_norm, iso;  // the solver's scalars
-    int ok, done, converged, iters;
-    unsigned ticket;
-};
 
 struct Ps {
     const double *pts, *nrm;
@@ -78,14 +69,13 @@ struct Ps {
     double scale, tol;
     int max_iter;
     PsState* st;
-    double* arr[5];  // R^3 (padded to whole tiles) fp64 each
+    double* arr[7];  // R^3 (padded to whole tiles) fp64 each; [5] = W and [6] only where the call needs them
     double* part;    // [kMaxTiles] partial sums
     double* lohi;    // [kBoxBlocks][6]
     int *hist, *sidx, *bsum;
     int *key[2], *idx[2], *rs_hist;  // the radix sort's two (key, index) buffers and its [digit][workgroup] counts
+    double *fs, *sp;                 // the screened solve's sorted fractions [3][n] and (B p) [n]
 };
-
-__device__ __forceinline__ size_t lin(int i, int j, int k, int R) { return ((size_t)k * R + j) * R + i; }
 
 // ---- orientation ----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_po_orient(const double* pts, double* nrm, int n, const double* views, int m) {
@@ -100,34 +90,6 @@ __global__ __launch_bounds__(256) void k_po_orient(const double* pts, double* nr
     }
     double* q = nrm + 3 * (size_t)i;
     if ((q[0] * cx + q[1] * cy) + q[2] * cz < 0) q[0] = -q[0], q[1] = -q[1], q[2] = -q[2];
-}
-
-// ---- fixed-order sums -------------------------------------------------------------------------------------------
-// The sum of v over every lane of the grid: block_sum's tree over the workgroup's 256 lanes, then the workgroups'
-// partials added by the workgroup that takes the last ticket.  True in that workgroup only, total in every lane.
-__device__ __forceinline__ bool grid_sum(double v, double* part, unsigned* ticket, double& total) {
-    __shared__ double s_red[4];
-    __shared__ int s_last;
-    const int nb = gridDim.x * gridDim.y * gridDim.z;
-    const int bid = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    double in[1] = {v}, out[1];
-    block_sum<1>(in, s_red, out);
-    if (threadIdx.x == 0) {
-        part[bid] = out[0];
-        __threadfence();  // the partial is visible to the device before the ticket is
-        s_last = atomicAdd(ticket, 1u) == (unsigned)nb - 1u;
-    }
-    __syncthreads();
-    if (!s_last) return false;
-    __threadfence();  // every partial was released before its ticket: none is read from a stale line
-    double acc = 0;
-    const volatile double* vp = part;
-    for (int b = threadIdx.x; b < nb; b += 256) acc += vp[b];
-    in[0] = acc;
-    block_sum<1>(in, s_red, out);
-    total = out[0];
-    if (threadIdx.x == 0) *ticket = 0;  // the next launch starts counting again
-    return true;
 }
 
 // ---- the tiled exclusive scan of an int array (count a multiple of kTile), in place; *total = the sum ----------
@@ -226,6 +188,8 @@ __global__ __launch_bounds__(64) void k_ps_grid(Ps a) {
     st.rho = st.alpha = st.beta = st.rhs_norm = st.iso = 0;
     st.done = st.converged = st.iters = 0;
     st.ticket = 0;
+    st.cells = st.go = 0;
+    st.lambda = st.rz = 0;
 }
 
 // point i's base node b and fractions f: g = (p - o) / h, b = floor(g) kept inside [0, R - 2]
@@ -309,11 +273,14 @@ __global__ __launch_bounds__(256) void k_rs_scatter(Rs a) {
     a.idx_out[at] = a.idx_in ? a.idx_in[i] : i;
 }
 
+// DENSITY: step 2b's W as a fourth accumulator (the same weights in the same order), and the number of base cells
+// that hold a point — an integer count, so the atomic's order does not show.
+template <bool DENSITY>
 __global__ __launch_bounds__(256) void k_ps_gather(Ps a, size_t nodes) {
     const size_t nd = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (nd >= nodes) return;
     const int R = a.R, i = (int)(nd % R), j = (int)(nd / R % R), k = (int)(nd / ((size_t)R * R));
-    double vx = 0, vy = 0, vz = 0;
+    double vx = 0, vy = 0, vz = 0, ws = 0;
     for (int d = 0; d < 8 && a.st->ok; d++) {
         const int dx = d & 1, dy = (d >> 1) & 1, dz = d >> 2;
         const int ci = i - dx, cj = j - dy, ck = k - dz;
@@ -327,9 +294,26 @@ __global__ __launch_bounds__(256) void k_ps_gather(Ps a, size_t nodes) {
             ps_base(a, p, b, f);
             const double w = ((dx ? f[0] : 1.0 - f[0]) * (dy ? f[1] : 1.0 - f[1])) * (dz ? f[2] : 1.0 - f[2]);
             vx += w * a.nrm[3 * p], vy += w * a.nrm[3 * p + 1], vz += w * a.nrm[3 * p + 2];
+            if (DENSITY) ws += w;
         }
     }
     a.arr[0][nd] = vx, a.arr[1][nd] = vy, a.arr[2][nd] = vz;
+    if (DENSITY) {
+        a.arr[5][nd] = ws;
+        const bool cell = a.st->ok && i <= R - 2 && j <= R - 2 && k <= R - 2 && a.hist[nd + 1] > a.hist[nd];
+        const unsigned long long m = __ballot(cell);
+        if (m && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(&a.st->cells, __popcll(m));
+    }
+}
+
+// the sorted point t's fractions, fs[axis][t]: the values k_ps_gather's weights are made of
+__global__ __launch_bounds__(256) void k_sc_frac(Ps a) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= a.n) return;
+    int b[3];
+    double f[3];
+    ps_base(a, (size_t)a.sidx[t], b, f);
+    for (int ax = 0; ax < 3; ax++) a.fs[(size_t)ax * a.n + t] = f[ax];
 }
 
 __global__ __launch_bounds__(256) void k_ps_div(Ps a, size_t nodes) {
@@ -472,6 +456,10 @@ struct Iso {
     int *voff, *toff;
     double* verts;
     int* tri;
+    // step 7 and the density output: W (null without either), the threshold, rho per written vertex (nullable)
+    const double* W;
+    double trim;
+    double* vdens;
 };
 __device__ const int kKind[8] = {-1, 0, 1, 3, 2, 4, 5, 6};
 __device__ const int kCorner[7] = {1, 2, 4, 3, 5, 6, 7};
@@ -493,86 +481,10 @@ __device__ __forceinline__ void tet_corners(int t, int vc[4]) {
     vc[0] = 0, vc[1] = 1 << p1, vc[2] = vc[1] | (1 << p2), vc[3] = 7;
 }
 
-__global__ __launch_bounds__(256) void k_iso_mask(Iso a, size_t padded) {
-    const size_t nd = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (nd >= padded) return;
-    if (nd >= a.nodes) {  // the scan's padding
-        a.voff[nd] = 0, a.toff[nd] = 0;
-        return;
-    }
-    const int R = a.R, i = (int)(nd % R), j = (int)(nd / R % R), k = (int)(nd / ((size_t)R * R));
-    unsigned below, valid;
-    iso_corners(a, i, j, k, below, valid);
-    unsigned mask = 0;
-    for (int c = 1; c < 8; c++)
-        if (((valid >> c) & 1u) && ((below >> c) & 1u) != (below & 1u)) mask |= 1u << kKind[c];
-    int tris = 0;
-    if (valid == 0xffu)
-        for (int t = 0; t < 6; t++) {
-            int vc[4];
-            tet_corners(t, vc);
-            const int nb = ((below >> vc[0]) & 1) + ((below >> vc[1]) & 1) + ((below >> vc[2]) & 1) + ((below >> vc[3]) & 1);
-            tris += nb == 2 ? 2 : (nb == 1 || nb == 3) ? 1 : 0;
-        }
-    a.mask[nd] = (uint8_t)mask;
-    a.voff[nd] = __popc(mask), a.toff[nd] = tris;
-}
-
-__global__ __launch_bounds__(256) void k_iso_verts(Iso a) {
-    const size_t nd = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (nd >= a.nodes) return;
-    const unsigned mask = a.mask[nd];
-    if (!mask) return;
-    const int R = a.R, ijk[3] = {(int)(nd % R), (int)(nd / R % R), (int)(nd / ((size_t)R * R))};
-    const double h = a.geo[3], iso = a.geo[4], fa = a.field[nd];
-    int at = a.voff[nd];
-    for (int kind = 0; kind < 7; kind++) {
-        if (!((mask >> kind) & 1u)) continue;
-        if (at >= a.vcap) return;
-        const int c = kCorner[kind], d[3] = {c & 1, (c >> 1) & 1, c >> 2};
-        const double fb = a.field[lin(ijk[0] + d[0], ijk[1] + d[1], ijk[2] + d[2], R)];
-        const double t = (iso - fa) / (fb - fa);
-        for (int ax = 0; ax < 3; ax++) {
-            const double pa = a.geo[ax] + h * (double)ijk[ax], pb = a.geo[ax] + h * (double)(ijk[ax] + d[ax]);
-            a.verts[3 * (size_t)at + ax] = pa + t * (pb - pa);
-        }
-        at++;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_iso_tris(Iso a) {
-    const size_t nd = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (nd >= a.nodes) return;
-    const int R = a.R, i = (int)(nd % R), j = (int)(nd / R % R), k = (int)(nd / ((size_t)R * R));
-    if (i > R - 2 || j > R - 2 || k > R - 2) return;
-    unsigned below, valid;
-    iso_corners(a, i, j, k, below, valid);
-    if (below == 0 || below == 0xffu) return;
-    int at = a.toff[nd];
-    // the vertex on the edge between corners ca and cb (ca's bits inside cb's)
-    auto vid = [&](int ca, int cb) {
-        const size_t owner = nd + (ca & 1) + (size_t)((ca >> 1) & 1) * R + (size_t)(ca >> 2) * R * R;
-        return a.voff[owner] + __popc(a.mask[owner] & ((1u << kKind[cb - ca]) - 1u));
-    };
-    // a triangle over the edges (ea[e], eb[e]): wound from below to above on the doubled edge midpoints, smallest id first
-    auto emit = [&](const int ea[3], const int eb[3], int Dx, int Dy, int Dz) {
-        if (at >= a.tcap) return;
-        int m[3][3], id[3];
-        for (int e = 0; e < 3; e++) {
-            id[e] = vid(ea[e], eb[e]);
-            for (int ax = 0; ax < 3; ax++) m[e][ax] = ((ea[e] >> ax) & 1) + ((eb[e] >> ax) & 1);
-        }
-        const int ux = m[1][0] - m[0][0], uy = m[1][1] - m[0][1], uz = m[1][2] - m[0][2];
-        const int wx = m[2][0] - m[0][0], wy = m[2][1] - m[0][1], wz = m[2][2] - m[0][2];
-        const int dot = (uy * wz - uz * wy) * Dx + (uz * wx - ux * wz) * Dy + (ux * wy - uy * wx) * Dz;
-        if (!(dot > 0)) {
-            const int s = id[1];
-            id[1] = id[2], id[2] = s;
-        }
-        const int f = id[0] < id[1] ? (id[0] < id[2] ? 0 : 2) : (id[1] < id[2] ? 1 : 2);
-        int* out = a.tri + 3 * (size_t)at;
-        out[0] = id[f], out[1] = id[(f + 1) % 3], out[2] = id[(f + 2) % 3];
-    };
+// The triangles of the cube whose corners below are the bits of below, in step 6's order: emit(ea, eb, Dx, Dy, Dz) with
+// the triangle's three edges ea[e] -> eb[e] (cube corners, ea's bits inside eb's) and the direction from below to above.
+template <class F>
+__device__ __forceinline__ void cube_triangles(unsigned below, F&& emit) {
     for (int t = 0; t < 6; t++) {
         int vc[4];
         tet_corners(t, vc);
@@ -593,16 +505,151 @@ __global__ __launch_bounds__(256) void k_iso_tris(Iso a) {
             edge(lo[0], hi[0], qa[0], qb[0]), edge(lo[0], hi[1], qa[1], qb[1]);
             edge(lo[1], hi[1], qa[2], qb[2]), edge(lo[1], hi[0], qa[3], qb[3]);
             for (int e = 0; e < 3; e++) ea[e] = qa[e], eb[e] = qb[e];
-            emit(ea, eb, Dx, Dy, Dz), at++;
+            emit(ea, eb, Dx, Dy, Dz);
             ea[1] = qa[2], eb[1] = qb[2], ea[2] = qa[3], eb[2] = qb[3];
-            emit(ea, eb, Dx, Dy, Dz), at++;
+            emit(ea, eb, Dx, Dy, Dz);
         } else {
             const int s = nb == 1 ? lo[0] : hi[0];
             for (int v = 0, e = 0; v < 4; v++)
                 if (v != s) edge(s, v, ea[e], eb[e]), e++;
-            emit(ea, eb, Dx, Dy, Dz), at++;
+            emit(ea, eb, Dx, Dy, Dz);
         }
     }
+}
+
+// Step 7 inside a cube with all eight corners: bit 8 ca + cb = the vertex on the edge ca -> cb exists and survives,
+// rho = W[a] + t (W[b] - W[a]) >= trim with step 6's t.  The expression is the one the edge's owner evaluates in
+// k_iso_verts, on the same operands: every cube that shares an edge decides alike.  Corners outside the grid read 0 and
+// their edges stay dead.  The loops are unrolled, so the corner values stay in registers.
+__device__ __forceinline__ unsigned long long iso_alive(const Iso& a, size_t nd, unsigned below, unsigned valid) {
+    const double iso = a.geo[4];
+    const size_t R = a.R;
+    double f[8], w[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        const size_t at = nd + (c & 1) + ((c >> 1) & 1) * R + (c >> 2) * R * R;
+        const bool in = (valid >> c) & 1u;
+        f[c] = in ? a.field[at] : 0.0, w[c] = in ? a.W[at] : 0.0;
+    }
+    unsigned long long alive = 0;
+#pragma unroll
+    for (int ca = 0; ca < 7; ca++)
+#pragma unroll
+        for (int cb = ca + 1; cb < 8; cb++) {
+            if ((ca & cb) != ca || !((valid >> cb) & 1u)) continue;  // cb in the grid: ca is too
+            if (((below >> ca) & 1u) == ((below >> cb) & 1u)) continue;
+            const double t = (iso - f[ca]) / (f[cb] - f[ca]);
+            if (w[ca] + t * (w[cb] - w[ca]) >= a.trim) alive |= 1ull << (8 * ca + cb);
+        }
+    return alive;
+}
+
+// TRIM (step 7): the mask keeps the surviving vertices only, and a cube counts the triangles whose three vertices
+// survive, so the scans hand out compacted ids and offsets and nothing is compacted afterwards.
+template <bool TRIM>
+__global__ __launch_bounds__(256) void k_iso_mask(Iso a, size_t padded) {
+    const size_t nd = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (nd >= padded) return;
+    if (nd >= a.nodes) {  // the scan's padding
+        a.voff[nd] = 0, a.toff[nd] = 0;
+        return;
+    }
+    const int R = a.R, i = (int)(nd % R), j = (int)(nd / R % R), k = (int)(nd / ((size_t)R * R));
+    unsigned below, valid;
+    iso_corners(a, i, j, k, below, valid);
+    unsigned long long alive = 0;
+    if (TRIM && below != 0 && below != valid) alive = iso_alive(a, nd, below, valid);
+    unsigned mask = 0;
+    for (int c = 1; c < 8; c++)
+        if (((valid >> c) & 1u) && ((below >> c) & 1u) != (below & 1u) && (!TRIM || ((alive >> c) & 1ull)))
+            mask |= 1u << kKind[c];
+    int tris = 0;
+    if (valid == 0xffu) {
+        if (TRIM) {
+            cube_triangles(below, [&](const int ea[3], const int eb[3], int, int, int) {
+                tris += (int)((alive >> (8 * ea[0] + eb[0])) & (alive >> (8 * ea[1] + eb[1])) & (alive >> (8 * ea[2] + eb[2])) & 1ull);
+            });
+        } else {
+            for (int t = 0; t < 6; t++) {
+                int vc[4];
+                tet_corners(t, vc);
+                const int nb = ((below >> vc[0]) & 1) + ((below >> vc[1]) & 1) + ((below >> vc[2]) & 1) + ((below >> vc[3]) & 1);
+                tris += nb == 2 ? 2 : (nb == 1 || nb == 3) ? 1 : 0;
+            }
+        }
+    }
+    a.mask[nd] = (uint8_t)mask;
+    a.voff[nd] = __popc(mask), a.toff[nd] = tris;
+}
+
+// DENSITY: rho of each written vertex goes to vdens
+template <bool DENSITY>
+__global__ __launch_bounds__(256) void k_iso_verts(Iso a) {
+    const size_t nd = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (nd >= a.nodes) return;
+    const unsigned mask = a.mask[nd];
+    if (!mask) return;
+    const int R = a.R, ijk[3] = {(int)(nd % R), (int)(nd / R % R), (int)(nd / ((size_t)R * R))};
+    const double h = a.geo[3], iso = a.geo[4], fa = a.field[nd];
+    int at = a.voff[nd];
+    for (int kind = 0; kind < 7; kind++) {
+        if (!((mask >> kind) & 1u)) continue;
+        if (at >= a.vcap) return;
+        const int c = kCorner[kind], d[3] = {c & 1, (c >> 1) & 1, c >> 2};
+        const size_t nb = lin(ijk[0] + d[0], ijk[1] + d[1], ijk[2] + d[2], R);
+        const double fb = a.field[nb];
+        const double t = (iso - fa) / (fb - fa);
+        if (DENSITY) a.vdens[at] = a.W[nd] + t * (a.W[nb] - a.W[nd]);
+        for (int ax = 0; ax < 3; ax++) {
+            const double pa = a.geo[ax] + h * (double)ijk[ax], pb = a.geo[ax] + h * (double)(ijk[ax] + d[ax]);
+            a.verts[3 * (size_t)at + ax] = pa + t * (pb - pa);
+        }
+        at++;
+    }
+}
+
+// TRIM: a triangle is written when the masks of its three edges' owners still hold the vertices (k_iso_mask counted
+// it by the same rule)
+template <bool TRIM>
+__global__ __launch_bounds__(256) void k_iso_tris(Iso a) {
+    const size_t nd = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (nd >= a.nodes) return;
+    const int R = a.R, i = (int)(nd % R), j = (int)(nd / R % R), k = (int)(nd / ((size_t)R * R));
+    if (i > R - 2 || j > R - 2 || k > R - 2) return;
+    unsigned below, valid;
+    iso_corners(a, i, j, k, below, valid);
+    if (below == 0 || below == 0xffu) return;
+    int at = a.toff[nd];
+    // the vertex on the edge between corners ca and cb (ca's bits inside cb's)
+    auto vid = [&](int ca, int cb) {
+        const size_t owner = nd + (ca & 1) + (size_t)((ca >> 1) & 1) * R + (size_t)(ca >> 2) * R * R;
+        return a.voff[owner] + __popc(a.mask[owner] & ((1u << kKind[cb - ca]) - 1u));
+    };
+    auto alive = [&](int ca, int cb) {
+        const size_t owner = nd + (ca & 1) + (size_t)((ca >> 1) & 1) * R + (size_t)(ca >> 2) * R * R;
+        return (a.mask[owner] >> kKind[cb - ca]) & 1u;
+    };
+    // a triangle over the edges (ea[e], eb[e]): wound from below to above on the doubled edge midpoints, smallest id first
+    cube_triangles(below, [&](const int ea[3], const int eb[3], int Dx, int Dy, int Dz) {
+        if (TRIM && !(alive(ea[0], eb[0]) && alive(ea[1], eb[1]) && alive(ea[2], eb[2]))) return;  // not counted either
+        const int slot = at++;
+        if (slot >= a.tcap) return;
+        int m[3][3], id[3];
+        for (int e = 0; e < 3; e++) {
+            id[e] = vid(ea[e], eb[e]);
+            for (int ax = 0; ax < 3; ax++) m[e][ax] = ((ea[e] >> ax) & 1) + ((eb[e] >> ax) & 1);
+        }
+        const int ux = m[1][0] - m[0][0], uy = m[1][1] - m[0][1], uz = m[1][2] - m[0][2];
+        const int wx = m[2][0] - m[0][0], wy = m[2][1] - m[0][1], wz = m[2][2] - m[0][2];
+        const int dot = (uy * wz - uz * wy) * Dx + (uz * wx - ux * wz) * Dy + (ux * wy - uy * wx) * Dz;
+        if (!(dot > 0)) {
+            const int s = id[1];
+            id[1] = id[2], id[2] = s;
+        }
+        const int f = id[0] < id[1] ? (id[0] < id[2] ? 0 : 2) : (id[1] < id[2] ? 1 : 2);
+        int* out = a.tri + 3 * (size_t)slot;
+        out[0] = id[f], out[1] = id[(f + 1) % 3], out[2] = id[(f + 2) % 3];
+    });
 }
 
 __global__ void k_iso_geo(double* geo, double ox, double oy, double oz, double h, double iso) {
@@ -623,11 +670,12 @@ __global__ void k_ps_info(PsState* st, double* geo, double* info, int* counts, i
     if (!st->ok) counts[0] = counts[1] = 0;
 }
 
-#define PS_LAUNCH(kernel, grid, block, ...)                                          \
+#define PS_LAUNCH_AS(name, kernel, grid, block, ...)                                 \
     do {                                                                             \
-        ProfScope ps_(ctx, #kernel, s);                                              \
+        ProfScope ps_(ctx, name, s);                                                 \
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, s, __VA_ARGS__);      \
     } while (0)
+#define PS_LAUNCH(kernel, grid, block, ...) PS_LAUNCH_AS(#kernel, kernel, grid, block, __VA_ARGS__)
 
 size_t pad_tile(size_t v) { return (v + kTile - 1) / kTile * kTile; }
 // the point sort's workgroups, a multiple of 8 so that kRsBins counts each are whole scan tiles (the spare ones are empty)
@@ -649,11 +697,15 @@ int scan_enqueue(vs_ctx* ctx, int* data, size_t padded, int* bsum, int* total, h
 // the extraction's launches; mask [R^3] bytes, voff / toff [padded] ints, bsum [kMaxTiles], geo set on the device
 int iso_enqueue(vs_ctx* ctx, Iso a, int* bsum, int* d_counts, hipStream_t s) {
     const size_t padded = pad_tile(a.nodes);
-    PS_LAUNCH(k_iso_mask, blocks256(padded), 256, a, padded);
+    const bool trim = a.trim > 0;  // the variants are taken only then: the plain call runs the code it always ran
+    if (trim) PS_LAUNCH_AS("k_iso_mask", k_iso_mask<true>, blocks256(padded), 256, a, padded);
+    else PS_LAUNCH_AS("k_iso_mask", k_iso_mask<false>, blocks256(padded), 256, a, padded);
     VS_CHECK(scan_enqueue(ctx, a.voff, padded, bsum, d_counts, s));
     VS_CHECK(scan_enqueue(ctx, a.toff, padded, bsum, d_counts + 1, s));
-    PS_LAUNCH(k_iso_verts, blocks256(a.nodes), 256, a);
-    PS_LAUNCH(k_iso_tris, blocks256(a.nodes), 256, a);
+    if (a.vdens) PS_LAUNCH_AS("k_iso_verts", k_iso_verts<true>, blocks256(a.nodes), 256, a);
+    else PS_LAUNCH_AS("k_iso_verts", k_iso_verts<false>, blocks256(a.nodes), 256, a);
+    if (trim) PS_LAUNCH_AS("k_iso_tris", k_iso_tris<true>, blocks256(a.nodes), 256, a);
+    else PS_LAUNCH_AS("k_iso_tris", k_iso_tris<false>, blocks256(a.nodes), 256, a);
     VS_HIP(hipGetLastError());
     return VS_OK;
 }
@@ -670,8 +722,13 @@ int res_check(const char* who, int R, int min_r) {
     return VS_OK;
 }
 
-int poisson_check(const char* who, vs_cloud_poisson_config& c, int n) {
+// sc_iter: the screened loop's iterations; a max_iter of 0 is 8 R there too without a preconditioner, kScIters with it
+int poisson_check(const char* who, vs_cloud_poisson_config& c, int n, int* sc_iter) {
     VS_CHECK(res_check(who, c.resolution, VS_POISSON_MIN_RES));
+    if (!(c.point_weight >= 0) || !std::isfinite(c.point_weight) || !(c.trim >= 0) || !std::isfinite(c.trim)) {
+        set_error(std::string(who) + ": point_weight or trim negative or not finite");
+        return VS_ERR_ARG;
+    }
     if (n < 1 || !(c.scale > 1) || !std::isfinite(c.scale) || !(c.tol >= 0) || !std::isfinite(c.tol) || c.max_iter < 0) {
         set_error(std::string(who) + ": no points, scale not above 1, or a negative tol or max_iter");
         return VS_ERR_ARG;
@@ -680,6 +737,7 @@ int poisson_check(const char* who, vs_cloud_poisson_config& c, int n) {
         set_error(std::string(who) + ": solver is neither VS_POISSON_SOLVER_CG nor VS_POISSON_SOLVER_DIRECT");
         return VS_ERR_ARG;
     }
+    *sc_iter = c.max_iter ? c.max_iter : c.solver == VS_POISSON_SOLVER_DIRECT ? kScIters : 8 * c.resolution;
     if (c.max_iter == 0) c.max_iter = 8 * c.resolution;
     return cloud_size_check(who, n, 1, VS_CLOUD_GRID_MAX_POINTS);
 }
@@ -689,22 +747,29 @@ struct Plan {
     Ps a;
     Cg cg;
     Iso iso;
+    Sc sc;
     double* geo;
     size_t nodes, padded;
     int passes;  // radix passes that cover a cell index
+    bool density, screened;  // W is computed (arr[5]); step 4s runs (arr[6], the cells' starts apart, fs and sp)
 };
 
+// want_w: a density output is asked for.  Memory, fp64 arrays of R^3: five; six with W (trimming or a density output);
+// seven and the cells' starts as R^3 ints of their own with screening, whose loop needs the starts to the end:
+// 40, 48 and 60 R^3 bytes (+ 24 n for the point sort, + 32 n for the screened loop's sorted fractions and B p).
 int poisson_plan(vs_ctx* ctx, const double* d_pts, const double* d_nrm, int n, const vs_cloud_poisson_config& c,
-                 Plan* pl) {
+                 int sc_iter, bool want_w, Plan* pl) {
     Ps& a = pl->a;
     a = Ps{};
+    pl->screened = c.point_weight > 0, pl->density = pl->screened || c.trim > 0 || want_w;
+    const int arrays = pl->screened ? 7 : pl->density ? 6 : 5;
     a.pts = d_pts, a.nrm = d_nrm, a.n = n, a.R = c.resolution, a.scale = c.scale, a.tol = c.tol, a.max_iter = c.max_iter;
     const size_t nodes = (size_t)a.R * a.R * a.R, padded = pad_tile(nodes);
     pl->nodes = nodes, pl->padded = padded;
     pl->passes = 1;
     while (((nodes - 1) >> (pl->passes * kRsBits)) != 0) pl->passes++;  // nodes <= 2^27: at most 3
     VS_CHECK(carve_buf(ctx->cloud_poisson, [&](Carver& p) {
-        for (double*& v : a.arr) v = p.take<double>(padded);
+        for (int e = 0; e < arrays; e++) a.arr[e] = p.take<double>(padded);
         a.st = p.take<PsState>(1);
         pl->geo = p.take<double>(5);
         a.part = p.take<double>(kMaxTiles);
@@ -712,8 +777,9 @@ int poisson_plan(vs_ctx* ctx, const double* d_pts, const double* d_nrm, int n, c
         for (int e = 0; e < 2; e++) a.key[e] = p.take<int>(n), a.idx[e] = p.take<int>(n);
         a.rs_hist = p.take<int>((size_t)kRsBins * rs_blocks(n));
         a.bsum = p.take<int>(kMaxTiles);
+        if (pl->screened) a.hist = p.take<int>(padded), a.fs = p.take<double>(3 * (size_t)n), a.sp = p.take<double>(n);
     }));
-    a.hist = reinterpret_cast<int*>(a.arr[4]);  // free until the first k_cg_apply writes q
+    if (!pl->screened) a.hist = reinterpret_cast<int*>(a.arr[4]);  // free until the first k_cg_apply writes q
     a.sidx = a.idx[pl->passes & 1];
     Cg& g = pl->cg;
     g = Cg{};
@@ -724,6 +790,17 @@ int poisson_plan(vs_ctx* ctx, const double* d_pts, const double* d_nrm, int n, c
     o.field = a.arr[0], o.geo = pl->geo, o.R = a.R, o.nodes = nodes;
     o.mask = reinterpret_cast<uint8_t*>(a.arr[3]);
     o.voff = reinterpret_cast<int*>(a.arr[1]), o.toff = reinterpret_cast<int*>(a.arr[2]);
+    o.W = pl->density ? a.arr[5] : nullptr, o.trim = c.trim;
+    // Step 4s.  x, r, q and the p buffers are step 4's; arr[6] is z under the preconditioner, and the copy of div that
+    // conjugate gradients (which turn arr[3] into their residual) leave for b otherwise, where z is r.
+    const bool direct = c.solver == VS_POISSON_SOLVER_DIRECT;
+    Sc& sc = pl->sc;
+    sc = Sc{};
+    sc.st = a.st, sc.x = a.arr[0], sc.r = a.arr[3], sc.z = direct ? a.arr[6] : a.arr[3], sc.q = a.arr[4];
+    sc.p[0] = a.arr[1], sc.p[1] = a.arr[2], sc.W = a.arr[5], sc.div = direct ? a.arr[3] : a.arr[6];
+    sc.sp = a.sp, sc.part = a.part, sc.fs = a.fs, sc.skey = a.key[pl->passes & 1], sc.starts = a.hist;
+    sc.n = n, sc.R = a.R, sc.max_iter = sc_iter, sc.direct = direct, sc.nodes = nodes;
+    sc.tol = c.tol, sc.point_weight = c.point_weight;
     return VS_OK;
 }
 
@@ -744,7 +821,9 @@ int poisson_rhs(vs_ctx* ctx, Plan& pl, hipStream_t s) {
         VS_CHECK(scan_enqueue(ctx, rs.hist, (size_t)kRsBins * rs.nblocks, a.bsum, nullptr, s));
         PS_LAUNCH(k_rs_scatter, rs.nblocks, 256, rs);
     }
-    PS_LAUNCH(k_ps_gather, blocks256(pl.nodes), 256, a, pl.nodes);
+    if (pl.density) PS_LAUNCH_AS("k_ps_gather", k_ps_gather<true>, blocks256(pl.nodes), 256, a, pl.nodes);
+    else PS_LAUNCH_AS("k_ps_gather", k_ps_gather<false>, blocks256(pl.nodes), 256, a, pl.nodes);
+    if (pl.screened) PS_LAUNCH(k_sc_frac, blocks256(a.n), 256, a);
     PS_LAUNCH(k_ps_div, blocks256(pl.nodes), 256, a, pl.nodes);
     VS_HIP(hipGetLastError());
     return VS_OK;
@@ -778,13 +857,20 @@ int direct_solve(vs_ctx* ctx, Plan& pl, hipStream_t s) {
     return poisson_dst_enqueue(ctx, pl.a.arr[3], pl.a.arr[0], pl.a.arr[1], pl.a.arr[2], pl.a.R, 0.0, &ds, nullptr, s);
 }
 
+// step 4's chi in arr[0] -> tau (step 5 on chi0, left in st->iso), then the screened loop's start
+int screened_start(vs_ctx* ctx, Plan& pl, hipStream_t s) {
+    PS_LAUNCH(k_ps_iso, blocks256(pl.a.n), 256, pl.a, (const double*)pl.a.arr[0]);
+    VS_HIP(hipGetLastError());
+    return screen_start(ctx, pl.sc, s);
+}
+
 // chi in arr[0] -> iso, the mesh and the report
 int poisson_finish(vs_ctx* ctx, Plan& pl, int vcap, int tcap, double* d_verts, int* d_tri, int* d_counts,
-                   double* d_info, hipStream_t s) {
+                   double* d_info, double* d_vdens, hipStream_t s) {
     PS_LAUNCH(k_ps_iso, blocks256(pl.a.n), 256, pl.a, (const double*)pl.a.arr[0]);
     PS_LAUNCH(k_ps_info, 1, 64, pl.a.st, pl.geo, d_info, d_counts, 0);
     Iso o = pl.iso;
-    o.vcap = vcap, o.tcap = tcap, o.verts = d_verts, o.tri = d_tri;
+    o.vcap = vcap, o.tcap = tcap, o.verts = d_verts, o.tri = d_tri, o.vdens = d_vdens;
     VS_CHECK(iso_enqueue(ctx, o, pl.a.bsum, d_counts, s));
     PS_LAUNCH(k_ps_info, 1, 64, pl.a.st, pl.geo, d_info, d_counts, 1);
     VS_HIP(hipGetLastError());
@@ -850,6 +936,8 @@ void vs_cloud_poisson_default_config(vs_cloud_poisson_config* c) {
     c->tol = 1e-6;
     c->max_iter = 0;      // 8 * resolution
     c->solver = VS_POISSON_SOLVER_CG;
+    c->point_weight = 0;  // PoissonRecon --pointWeight; the reference's command passes 6
+    c->trim = 0;          // SurfaceTrimmer --trim, in units of W
 }
 
 int vs_cloud_orient_normals_dev(vs_ctx* ctx, const double* d_pts, double* d_normals, int n, const double* d_views, int m,
@@ -925,36 +1013,58 @@ int vs_grid_isosurface(vs_ctx* ctx, const double* field, int resolution, const d
     return mesh_to_host(s, counts, vcap, tcap, d_verts, d_tri, verts, tri);
 }
 
-int vs_cloud_poisson_dev(vs_ctx* ctx, const double* d_pts, const double* d_normals, int n,
-                         const vs_cloud_poisson_config* cfg, int vcap, int tcap, double* d_verts, int* d_tri,
-                         int* d_counts, double* d_info, void* stream) {
+int vs_cloud_poisson_density_dev(vs_ctx* ctx, const double* d_pts, const double* d_normals, int n,
+                                 const vs_cloud_poisson_config* cfg, int vcap, int tcap, double* d_verts, int* d_tri,
+                                 int* d_counts, double* d_info, double* d_vert_density, void* stream) {
     VS_ARG(ctx && d_pts && d_normals && d_counts && d_info && vcap >= 0 && tcap >= 0 && (vcap == 0 || d_verts) &&
                (tcap == 0 || d_tri),
            "vs_cloud_poisson_dev: null argument or bad size");
     vs_cloud_poisson_config c = config_or(cfg, vs_cloud_poisson_default_config);
-    VS_CHECK(poisson_check("vs_cloud_poisson_dev", c, n));
+    int sc_iter;
+    VS_CHECK(poisson_check("vs_cloud_poisson_dev", c, n, &sc_iter));
     VS_HIP(hipSetDevice(ctx->device));
     const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     Plan pl;
-    VS_CHECK(poisson_plan(ctx, d_pts, d_normals, n, c, &pl));
+    VS_CHECK(poisson_plan(ctx, d_pts, d_normals, n, c, sc_iter, d_vert_density != nullptr, &pl));
     VS_CHECK(poisson_rhs(ctx, pl, s));
     if (c.solver == VS_POISSON_SOLVER_DIRECT) {
         VS_CHECK(direct_solve(ctx, pl, s));
     } else {
+        if (pl.screened) VS_HIP(hipMemcpyAsync(pl.a.arr[6], pl.a.arr[3], pl.nodes * sizeof(double), hipMemcpyDeviceToDevice, s));
         VS_CHECK(cg_start(ctx, pl, s));
         VS_CHECK(cg_iterate(ctx, pl, 0, c.max_iter, s));
     }
-    return poisson_finish(ctx, pl, vcap, tcap, d_verts, d_tri, d_counts, d_info, s);
+    if (pl.screened) {
+        VS_CHECK(screened_start(ctx, pl, s));
+        VS_CHECK(screen_iterate(ctx, pl.sc, 0, sc_iter, s));
+    }
+    return poisson_finish(ctx, pl, vcap, tcap, d_verts, d_tri, d_counts, d_info, d_vert_density, s);
+}
+
+int vs_cloud_poisson_dev(vs_ctx* ctx, const double* d_pts, const double* d_normals, int n,
+                         const vs_cloud_poisson_config* cfg, int vcap, int tcap, double* d_verts, int* d_tri,
+                         int* d_counts, double* d_info, void* stream) {
+    return vs_cloud_poisson_density_dev(ctx, d_pts, d_normals, n, cfg, vcap, tcap, d_verts, d_tri, d_counts, d_info,
+                                        nullptr, stream);
 }
 
 int vs_cloud_poisson(vs_ctx* ctx, const double* pts, const double* normals, int n, const double* views, int m,
                      const vs_cloud_poisson_config* cfg, int vcap, int tcap, double* verts, int* tri, int counts[2],
                      double info[4], double* normals_out, double* rhs_out, double* field_out) {
+    return vs_cloud_poisson_density(ctx, pts, normals, n, views, m, cfg, vcap, tcap, verts, tri, counts, info,
+                                    normals_out, rhs_out, field_out, nullptr, nullptr);
+}
+
+int vs_cloud_poisson_density(vs_ctx* ctx, const double* pts, const double* normals, int n, const double* views, int m,
+                             const vs_cloud_poisson_config* cfg, int vcap, int tcap, double* verts, int* tri,
+                             int counts[2], double info[4], double* normals_out, double* rhs_out, double* field_out,
+                             double* density_out, double* vert_density) {
     VS_ARG(ctx && pts && counts && info && vcap >= 0 && tcap >= 0 && (vcap == 0 || verts) && (tcap == 0 || tri) &&
                (normals || views),
            "vs_cloud_poisson: null argument, bad size, or neither normals nor views");
     vs_cloud_poisson_config c = config_or(cfg, vs_cloud_poisson_default_config);
-    VS_CHECK(poisson_check("vs_cloud_poisson", c, n));
+    int sc_iter;
+    VS_CHECK(poisson_check("vs_cloud_poisson", c, n, &sc_iter));
     if (views) VS_CHECK(orient_check("vs_cloud_poisson", n, m));
     double ext = 0;  // the box's largest edge, before the staging is sized
     for (int ax = 0; ax < 3; ax++) {
@@ -966,7 +1076,7 @@ int vs_cloud_poisson(vs_ctx* ctx, const double* pts, const double* normals, int 
     VS_HIP(hipSetDevice(ctx->device));
     const hipStream_t s = ctx->stream;
     const size_t pb = (size_t)n * 3 * sizeof(double);
-    double *d_in, *d_nrm, *d_views, *d_verts, *d_info;
+    double *d_in, *d_nrm, *d_views, *d_verts, *d_info, *d_vdens = nullptr;
     int *d_tri, *d_counts;
     VS_CHECK(carve_buf(ctx->h_aux0, [&](Carver& h) {
         d_in = h.take<double>((size_t)n * 3);
@@ -976,6 +1086,7 @@ int vs_cloud_poisson(vs_ctx* ctx, const double* pts, const double* normals, int 
         d_tri = h.take<int>((size_t)std::max(tcap, 1) * 3);
         d_counts = h.take<int>(2);
         d_info = h.take<double>(4);
+        if (vert_density) d_vdens = h.take<double>(std::max(vcap, 1));
     }));
     VS_HIP(hipMemcpyAsync(d_in, pts, pb, hipMemcpyHostToDevice, s));
     if (normals) {
@@ -989,23 +1100,37 @@ int vs_cloud_poisson(vs_ctx* ctx, const double* pts, const double* normals, int 
     }
     if (normals_out) VS_HIP(hipMemcpyAsync(normals_out, d_nrm, pb, hipMemcpyDeviceToHost, s));
     Plan pl;
-    VS_CHECK(poisson_plan(ctx, d_in, d_nrm, n, c, &pl));
+    VS_CHECK(poisson_plan(ctx, d_in, d_nrm, n, c, sc_iter, density_out || vert_density, &pl));
     VS_CHECK(poisson_rhs(ctx, pl, s));
     if (rhs_out) VS_HIP(hipMemcpyAsync(rhs_out, pl.a.arr[3], pl.nodes * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (c.solver == VS_POISSON_SOLVER_DIRECT) VS_CHECK(direct_solve(ctx, pl, s));
+    if (density_out) VS_HIP(hipMemcpyAsync(density_out, pl.a.arr[5], pl.nodes * sizeof(double), hipMemcpyDeviceToHost, s));
+    const bool direct = c.solver == VS_POISSON_SOLVER_DIRECT;
+    if (!direct && pl.screened) VS_HIP(hipMemcpyAsync(pl.a.arr[6], pl.a.arr[3], pl.nodes * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (direct) VS_CHECK(direct_solve(ctx, pl, s));
     else VS_CHECK(cg_start(ctx, pl, s));
-    for (int it = 0; it < c.max_iter && c.solver == VS_POISSON_SOLVER_CG; it += kPoll) {
+    for (int it = 0; it < c.max_iter && !direct; it += kPoll) {
         int done = 0;
         VS_HIP(hipMemcpyAsync(&done, &pl.a.st->done, sizeof(int), hipMemcpyDeviceToHost, s));
         VS_HIP(hipStreamSynchronize(s));
         if (done) break;
         VS_CHECK(cg_iterate(ctx, pl, it, std::min(it + kPoll, c.max_iter), s));
     }
+    if (pl.screened) VS_CHECK(screened_start(ctx, pl, s));
+    const int poll = direct ? kScPoll : kPoll;
+    for (int it = 0; it < sc_iter && pl.screened; it += poll) {
+        int go = 0;
+        VS_HIP(hipMemcpyAsync(&go, &pl.a.st->go, sizeof(int), hipMemcpyDeviceToHost, s));
+        VS_HIP(hipStreamSynchronize(s));
+        if (!go) break;
+        VS_CHECK(screen_iterate(ctx, pl.sc, it, std::min(it + poll, sc_iter), s));
+    }
     if (field_out) VS_HIP(hipMemcpyAsync(field_out, pl.a.arr[0], pl.nodes * sizeof(double), hipMemcpyDeviceToHost, s));
-    VS_CHECK(poisson_finish(ctx, pl, vcap, tcap, d_verts, d_tri, d_counts, d_info, s));
+    VS_CHECK(poisson_finish(ctx, pl, vcap, tcap, d_verts, d_tri, d_counts, d_info, d_vdens, s));
     VS_HIP(hipMemcpyAsync(counts, d_counts, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     VS_HIP(hipMemcpyAsync(info, d_info, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
     VS_HIP(hipStreamSynchronize(s));
+    const int nv = std::min(vcap, counts[0]);
+    if (vert_density && nv > 0) VS_HIP(hipMemcpyAsync(vert_density, d_vdens, (size_t)nv * sizeof(double), hipMemcpyDeviceToHost, s));
     return mesh_to_host(s, counts, vcap, tcap, d_verts, d_tri, verts, tri);
 }
 

@@ -279,6 +279,7 @@ int poisson_dst_enqueue(vs_ctx* ctx, const double* d_div, double* d_chi, double*
     a.R = R, a.Rp = (R + 15) / 16 * 16, a.h = h;
     a.c3 = (2.0 / (double)(R + 1)) * (2.0 / (double)(R + 1)) * (2.0 / (double)(R + 1));
     if (st) a.ok = st->ok, a.d_h = st->h;
+    if (st && st->precond) a.c3 = -a.c3;
     const long long R1 = R, R2 = R1 * R1;
     const unsigned cols = (unsigned)((R2 + kTN - 1) / kTN), rowt = (unsigned)((R + kTN - 1) / kTN);
     auto along_i = [&](const double* x, double* y) {
@@ -302,6 +303,10 @@ int poisson_dst_enqueue(vs_ctx* ctx, const double* d_div, double* d_chi, double*
     }
     along_j(t0, t1);
     along_i(t1, d_chi);
+    if (st && st->precond) {
+        VS_HIP(hipGetLastError());
+        return VS_OK;
+    }
     DstRes r{};
     r.chi = d_chi, r.rhs = d_div, r.part = part, r.ok = a.ok, r.d_h = a.d_h, r.h = h, r.R = R;
     r.nodes = (size_t)R2 * R, r.blocks = (int)((r.nodes + kResTile - 1) / kResTile), r.info = d_info;

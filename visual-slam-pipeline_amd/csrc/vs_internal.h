@@ -333,12 +333,16 @@ int cloud_densify(vs_ctx* ctx, const double* d_pts, int n_max, const vs_cloud_de
 // the scratch fields t0 and t1 (R^3 each, apart from d_div and d_chi; d_div is read again by the residual pass after
 // d_chi is written, so the two differ).  st (nullable): cloud_poisson.hip's state block on the device — ok and h are read there, and
 // rho, rhs_norm and converged written as its report expects; without it h is the host's.  d_info (nullable) =
-// {0, relative residual}.  Enqueue only, but for the table's upload on the first call with a new R.
+// {0, relative residual}.  precond (poisson_screen.hip's preconditioner): d_chi = +A^-1 d_div (the scale's sign is
+// turned, which is exact), no residual pass and nothing reported; ok is then the screened loop's flag, so that the
+// passes return at once after the loop has stopped, and d_chi may be anything but t0 and t1.
+// Enqueue only, but for the table's upload on the first call with a new R.
 struct DstState {
     const int* ok;
     const double* h;
     double *rho, *rhs_norm;
     int* converged;
+    int precond = 0;
 };
 int poisson_dst_enqueue(vs_ctx* ctx, const double* d_div, double* d_chi, double* t0, double* t1, int R, double h,
                         const DstState* st, double* d_info, hipStream_t s);

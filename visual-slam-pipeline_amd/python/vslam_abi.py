@@ -135,6 +135,8 @@ _SIG = {
     "vs_grid_poisson_solve": (_I, [_P, _P, _I, ctypes.c_double, _P, _P]),
     "vs_cloud_poisson_dev": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "vs_cloud_poisson": (_I, [_P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "vs_cloud_poisson_density_dev": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "vs_cloud_poisson_density": (_I, [_P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vs_slam_loops": (_I, [_P, _I, _P, _P, _P, _P]),
     "vs_pose_graph_optimize": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, ctypes.c_double, _I, _P, _P]),
     "vs_pgo_transform_points": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P]),
@@ -678,7 +680,8 @@ class Context:
     # ---- Poisson surface reconstruction (main.cpp:1379-1458 --poisson; the semantics are vslam_abi.h's) ----
     def poisson_config(self, **overrides):
         """vs_cloud_poisson_config with the defaults (resolution 256, scale 1.1, tol 1e-6, max_iter 0 = 8 resolution,
-        solver 0 = conjugate gradients; 1 = the direct solve by sine transforms)."""
+        solver 0 = conjugate gradients; 1 = the direct solve by sine transforms; point_weight 0 = no screening,
+        trim 0 = no density trimming)."""
         cfg = CloudPoissonConfig()
         self.lib.vs_cloud_poisson_default_config(ctypes.byref(cfg))
         for k, v in overrides.items():
@@ -739,11 +742,19 @@ class Context:
         _check(self.lib.vs_cloud_poisson_dev(self.h, d_pts, d_normals, n, None if cfg is None else ctypes.byref(cfg), vcap,
                                              tcap, d_verts, d_tri, d_counts, d_info, stream))
 
-    def cloud_poisson(self, pts, normals=None, views=None, vcap=1 << 20, tcap=1 << 21, fields=False, **cfg):
+    def cloud_poisson_density_dev(self, d_pts, d_normals, n, cfg, vcap, tcap, d_verts, d_tri, d_counts, d_info,
+                                  d_vert_density=None, stream=None):
+        """cloud_poisson_dev with d_vert_density [vcap] fp64 (or None): the density of each written vertex."""
+        _check(self.lib.vs_cloud_poisson_density_dev(self.h, d_pts, d_normals, n, None if cfg is None else ctypes.byref(cfg),
+                                                     vcap, tcap, d_verts, d_tri, d_counts, d_info, d_vert_density, stream))
+
+    def cloud_poisson(self, pts, normals=None, views=None, vcap=1 << 20, tcap=1 << 21, fields=False, density=None, **cfg):
         """Host points [n, 3], normals (None: estimated with k = 20) and views (None: the normals are taken as oriented)
         -> dict(verts, tri, counts [2] = vertices, triangles, info [4] = iterations, relative residual, iso, converged,
-        normals = the normals used; with fields also rhs and chi [R, R, R] indexed [k, j, i]).  cfg:
-        vs_cloud_poisson_config fields."""
+        normals = the normals used; with fields also rhs and chi [R, R, R] indexed [k, j, i]).  density=True adds
+        vert_density [vertices] and, with fields, density = W [R, R, R]; density=False goes through
+        vs_cloud_poisson_density with neither output, None through vs_cloud_poisson.  cfg: vs_cloud_poisson_config
+        fields."""
         p = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
         n = p.shape[0]
         c = self.poisson_config(**cfg)
@@ -755,11 +766,18 @@ class Context:
         rhs, chi = (None, None) if cube is None else (np.zeros(cube), np.zeros(cube))
         verts, tri = np.zeros((max(vcap, 1), 3)), np.zeros((max(tcap, 1), 3), np.int32)
         counts, info, used = np.zeros(2, np.int32), np.zeros(4), np.zeros((max(n, 1), 3))
-        _check(self.lib.vs_cloud_poisson(self.h, _ptr(p), opt(nrm), n, opt(v), 0 if v is None else len(v),
-                                         ctypes.byref(c), vcap, tcap, _ptr(verts), _ptr(tri), _ptr(counts), _ptr(info),
-                                         _ptr(used), opt(rhs), opt(chi)))
+        args = (self.h, _ptr(p), opt(nrm), n, opt(v), 0 if v is None else len(v), ctypes.byref(c), vcap, tcap,
+                _ptr(verts), _ptr(tri), _ptr(counts), _ptr(info), _ptr(used), opt(rhs), opt(chi))
+        if density is None:
+            _check(self.lib.vs_cloud_poisson(*args))
+            extra = {}
+        else:
+            W = np.zeros(cube) if density and cube is not None else None
+            vd = np.zeros(max(vcap, 1)) if density else None
+            _check(self.lib.vs_cloud_poisson_density(*args, opt(W), opt(vd)))
+            extra = dict(vert_density=vd[:min(vcap, counts[0])], density=W) if density else {}
         return dict(verts=verts[:min(vcap, counts[0])], tri=tri[:min(tcap, counts[1])], counts=counts, info=info,
-                    normals=used[:n], rhs=rhs, chi=chi)
+                    normals=used[:n], rhs=rhs, chi=chi, **extra)
 
     # ---- profiling ----
     def spcf_write_dev(self, path, frame_idx, F, d_kps, d_desc, d_n, cap, append=False, stream=None):
@@ -1001,7 +1019,8 @@ class CloudMeshConfig(ctypes.Structure):
 class CloudPoissonConfig(ctypes.Structure):
     """vs_cloud_poisson_config (Context.poisson_config fills in the defaults)."""
     _fields_ = [("resolution", ctypes.c_int), ("scale", ctypes.c_double), ("tol", ctypes.c_double),
-                ("max_iter", ctypes.c_int), ("solver", ctypes.c_int)]
+                ("max_iter", ctypes.c_int), ("solver", ctypes.c_int), ("point_weight", ctypes.c_double),
+                ("trim", ctypes.c_double)]
 
 
 # ---- F4: dense voxel fusion (main.cpp:1081-1146) ----------------------------------------------
